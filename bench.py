@@ -1,11 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark: skeletons/s solved to convergence (fixed 16 iterations) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--dump-outputs DIR] [--full]
 
 One *step* = one mbik_solve() over this rank's batch of skeletons (BASELINE.json
 configs[1] = C2 by default: 4096 x 32 bones / 4 effectors / 2 Kusudama cones per bone,
 16 iterations), inputs already resident in HBM.  Rank 0 prints one JSON line.
+
+A plain run does only what `value` needs: plan, autotune (part of warmup), W warmup steps, K timed
+steps, the result line.  --dump-outputs DIR then also writes the poses the last timed step left
+in the output buffer (what a caller of mbik_solve receives) as DIR/pose_out.npy, float32; the
+inputs come from a seeded generator, so two builds can be compared output for output.  Every
+other measurement and check described below (the timed gathers, library_multi, the rocprofv3
+counter passes, the PCIe-inclusive rate, the oracle parity check, the CPU baseline) runs only
+with --full.
 
 N > 1 runs one rank per GPU.  Under torch.distributed.run (WORLD_SIZE set) this process is
 a rank; WORLD_SIZE must equal --gpus.  Run as a plain command with --gpus N > 1, it starts
@@ -14,14 +22,14 @@ with its status.  Every rank solves its own contiguous shard of skeletons with n
 collective on the data path:
   --scaling weak    (default) the config's skeletons_per_gpu on every rank;
   --scaling strong  the config's whole batch (C4: 262,144) split by dist.shard_range.
-The RCCL gathers of the output poses are timed separately after the solve loop.  At N > 1
-rank 0 then also times the library's own multi-GPU path (mbik_multi_solve: one process, one
+With --full the RCCL gathers of the output poses are timed separately after the solve loop, and
+at N > 1 rank 0 then also times the library's own multi-GPU path (mbik_multi_solve: one process, one
 plan per visible device, peer-copy scatter / gather to device 0) over the whole batch while the
 other ranks wait on the host; it is reported under "library_multi", never as `value`.
 (--library-multi-devices 0,0 runs that measurement at N = 1 with the listed devices' plans:
 the one-GPU test of the same code.)
 
-At N = 1, after the timed region, rank 0 re-runs the timed layout in rocprofv3 --pmc child
+At N = 1 with --full, after the timed region, rank 0 re-runs the timed layout in rocprofv3 --pmc child
 processes (FETCH_SIZE, WRITE_SIZE, SQ wave counters; `--pmc off` skips them): the line's
 roofline.traffic and pmc_live.per_wave come from this run, not from committed files.
 
@@ -63,6 +71,12 @@ def parse():
     ap.add_argument("--skeletons", type=int, default=0,
                     help="skeletons per GPU (weak) or in total (strong); default: the config's")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beside the headline figure: timed gathers, library_multi, "
+                         "live counter passes, PCIe-inclusive rate, oracle parity, CPU baseline (each has its own switch below)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's output poses as DIR/pose_out.npy (float32; "
+                         "pose_out_rank<r>.npy at N > 1; a fixed seeded sample of skeletons above 64 MB)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU-only plumbing check: gloo, no GPU, no solve (tests)")
     ap.add_argument("--lanes", type=int, default=0, help="lanes per skeleton override (0 = plan default)")
@@ -241,13 +255,18 @@ def main():
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     wall_max = float(elapsed.item())
 
+    dump = None
+    if args.dump_outputs:
+        progress("dump outputs")
+        dump = dump_outputs(args.dump_outputs, pose_out.cpu().numpy(), rank, world)
+
     gather = None
-    if dist:
+    if dist and args.full:
         gather = timed_gathers(pose_out, total, dist, lambda: torch.cuda.synchronize(dev), torch.device(dev))
 
     # PCIe-inclusive rate (host buffers in, solve, host buffers out): reported, never `value`
     pcie = None
-    if rank == 0 and args.pmc != "child":
+    if args.full and rank == 0 and args.pmc != "child":
         plan.solve_host(wl.pose, wl.targets)
         reps = 5
         h0 = time.perf_counter()
@@ -260,7 +279,7 @@ def main():
     # parity spot check against the oracle (not timed): this rank's first 32 and last 32
     # skeletons, so the largest per-skeleton offsets of the timed launch are checked too
     parity = None
-    if not args.no_parity and rank == 0 and args.pmc != "child":
+    if args.full and not args.no_parity and rank == 0 and args.pmc != "child":
         progress("parity")
         try:
             from oracle import pyoracle as po
@@ -291,7 +310,7 @@ def main():
     # the library's single-process multi-GPU path (mbik_multi_*), after everything above
     lib_multi = None
     lm_devices = [int(x) for x in args.library_multi_devices.split(",") if x] or (list(range(world)) if world > 1 else [])
-    if lm_devices and not args.constraint_mode:
+    if args.full and lm_devices and not args.constraint_mode:
         if dist:
             dist.barrier(group=host_group)
         if rank == 0:
@@ -320,7 +339,7 @@ def main():
     # the PMC traffic of exactly the layout timed here (autotune may pick differently per box)
     tkey = key + "_" + layout_key(info)
     live = None
-    if pmc_enabled(args, world):
+    if args.full and pmc_enabled(args, world):
         progress("live counter passes")
         live = live_pmc(args, info, cfg, n)
     traffic_source = None
@@ -412,6 +431,8 @@ def main():
         "pcie_inclusive": pcie,
         "parity": parity,
     }
+    if dump is not None:
+        out["dump_outputs"] = dump
     if live is not None:
         out["pmc_live"] = live
     if lib_multi is not None:
@@ -420,7 +441,7 @@ def main():
         out["backend"] = backend
     if os.environ.get("MBIK_BENCH_DEVICE"):
         out["rehearsal"] = f"all {world} ranks on cuda:{local_rank} (MBIK_BENCH_DEVICE): not a scaling measurement"
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             progress("cpu baseline")
             out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds, **flags)
@@ -429,6 +450,28 @@ def main():
     print(json.dumps(out))
     if dist:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(directory: str, pose: np.ndarray, rank: int, world: int) -> dict:
+    """--dump-outputs: this rank's output poses after the last timed step, float32, as one .npy.
+    Above DUMP_LIMIT_BYTES (over all ranks) a fixed, seeded, sorted sample of skeletons is written:
+    the same skeletons in every run with the same arguments."""
+    os.makedirs(directory, exist_ok=True)
+    pose = np.ascontiguousarray(pose, dtype=np.float32)
+    per_skel = pose[0].nbytes if pose.shape[0] else 0
+    keep = pose.shape[0] if not per_skel else min(pose.shape[0], (DUMP_LIMIT_BYTES // max(1, world) - 4096) // per_skel)
+    sampled = keep < pose.shape[0]
+    if sampled:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(pose.shape[0], size=keep, replace=False))
+        pose = np.ascontiguousarray(pose[idx])
+    name = "pose_out.npy" if world == 1 else f"pose_out_rank{rank}.npy"
+    np.save(os.path.join(directory, name), pose)
+    return {"dir": directory, "file": name, "shape": list(pose.shape), "dtype": "float32", "sampled": sampled,
+            "sample_seed": DUMP_SAMPLE_SEED if sampled else None}
 
 
 def pin_layout(plan, info: dict) -> None:

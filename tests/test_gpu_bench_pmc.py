@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def run_bench(*extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "2", "--skeletons", "1024", "--steps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "2", "--skeletons", "1024", "--steps", "3",
            "--warmup", "1", "--no-cpu-baseline", "--no-parity", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -19,7 +19,7 @@ for CL in "$@"; do
     out=$OUT/${label}_c${CFG}_${L//:/_}_r$rep.json
     ( [ "$lib" != "-" ] && [ -n "$lib" ] && export MBIK_LIB_OVERRIDE=$PWD/$lib
       for e in ${envs//,/ }; do export "$e"; done
-      exec timeout -k 10 ${AB_TIMEOUT:-200} python bench.py --config $CFG --layout $L --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline \
+      exec timeout -k 10 ${AB_TIMEOUT:-200} python bench.py --full --config $CFG --layout $L --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline \
         ${EXTRA} > $out 2>$out.err ) || { echo "FAILED $label c$CFG"; tail -3 $out.err; exit 1; }
     python3 -c "import json;d=json.loads(open('$out').read().strip().splitlines()[-1]);print('$label', 'c$CFG', '$L', 'r$rep', round(d['ms_per_step'],4), (d.get('parity') or {}).get('bitwise_equal'))"
   done

@@ -11,7 +11,7 @@ for lib in "$@"; do
   for cfg in ${CFGS:-5 2}; do
     tag=$(basename $lib .so)
     if [ "$lib" = new ]; then unset MBIK_LIB_OVERRIDE; else export MBIK_LIB_OVERRIDE=$PWD/$lib; fi
-    timeout -k 10 300 python bench.py --config $cfg --constraint-mode \
+    timeout -k 10 300 python bench.py --full --config $cfg --constraint-mode \
       --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${tag}_c${cfg}_$rep.json 2> $OUT/${tag}_c${cfg}_$rep.err || exit $?
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], 'C$cfg', 'r$rep', round(d['ms_per_step'],3), 'ms', d['config']['lanes_per_skeleton'], d['config']['skeletons_per_block'], 'rw', d['config']['layout'].get('wave_roles'), d['parity'].get('bitwise_equal'))" $OUT/${tag}_c${cfg}_$rep.json $tag
   done

@@ -36,7 +36,7 @@ smoke() {
 }
 bench() { # <output name> <bench.py args...>
   local name=$1; shift
-  timeout -k 10 400 python -u bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err
+  timeout -k 10 400 python -u bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err
   local rc=$?; echo "bench[$*] rc=$rc"; tail -c 500 $OUT/$name.json; echo; return $rc
 }
 
@@ -58,7 +58,7 @@ final)
   bench c2_bench || exit 1
   mkdir -p $OUT/prof
   (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- \
-    python3 $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/c2_prof_bench.json 2> $OUT/c2_prof.err) || { echo "rocprof failed"; exit 1; }
+    python3 $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/c2_prof_bench.json 2> $OUT/c2_prof.err) || { echo "rocprof failed"; exit 1; }
   for c in 3 4 5; do bench c${c}_bench --config $c --steps 10 --warmup 2 || exit 1; done
   for c in 5 2; do bench c${c}_cmode_bench --config $c --constraint-mode --steps 10 --warmup 3 || exit 1; done
   echo "done $(date +%T)";;
@@ -71,7 +71,7 @@ counters)
     mkdir -p $O
     for ctr in FETCH_SIZE WRITE_SIZE; do
       (cd /tmp && TMPDIR=/tmp timeout -s KILL 240 rocprofv3 --pmc $ctr -d $O/$ctr -o run --output-format csv -- \
-        python3 $ROOT/bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-parity --layout ${LAY[$c]} \
+        python3 $ROOT/bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-parity --layout ${LAY[$c]} \
         > $O/$ctr.json 2> $O/$ctr.log) || { echo "c$c $ctr pass failed"; tail -5 $O/$ctr.log; exit 1; }
     done
     bash tools/valu_mix.sh $TAG/mix_c$c $c ${LAY[$c]} > $O/mix.log 2>&1 || { echo "c$c mix passes failed"; tail -5 $O/mix.log; exit 1; }
@@ -91,7 +91,7 @@ kstats)
   for kv in "${KA[@]}"; do
     n=${kv%%:*}; args=${kv#*:}
     (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/$n -o run --output-format csv -- \
-      python3 $ROOT/bench.py $args --steps 10 --warmup 3 --no-cpu-baseline > $OUT/$n.json 2> $OUT/$n.err) || { echo "$n failed"; exit 1; }
+      python3 $ROOT/bench.py --full $args --steps 10 --warmup 3 --no-cpu-baseline > $OUT/$n.json 2> $OUT/$n.err) || { echo "$n failed"; exit 1; }
     echo "$n done"
   done;;
 profile)

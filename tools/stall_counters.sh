@@ -16,7 +16,7 @@ for spec in "$@"; do
   n=$((n+1))
   CFG=${spec%%:*}; LAYOUT=${spec#*:}
   LA="--layout $LAYOUT"; [ "$LAYOUT" = auto ] && LA=
-  B="$ROOT/bench.py --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-parity $LA $EXTRA"
+  B="$ROOT/bench.py --full --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-parity $LA $EXTRA"
   i=0
   for G in "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM SQ_INSTS_VALU" \
            "SQ_WAVES SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAIT_INST_LDS" \

@@ -12,7 +12,7 @@ ROOT=$PWD
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="$ROOT/bench.py --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-parity"
+B="$ROOT/bench.py --full --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-parity"
 if [ -n "$LAYOUT" ]; then B="$B --layout $LAYOUT"; else B="$B --no-autotune"; fi
 i=0
 for G in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_INT32" \
