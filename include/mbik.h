@@ -17,6 +17,8 @@
  *   mbik_solve_host    <- same, synchronous, host buffers
  *   mbik_segment_solve <- IKBoneSegment3D::segment_solver()       src/ik_bone_segment_3d.cpp:210-225
  *                         (one call = one segment_solver() of one segment subtree)
+ *   mbik_pose_globals  <- Skeleton3D::get_bone_global_pose for every bone, as the reference calls
+ *                         it at src/ik_bone_3d.cpp:71 (and global * bind_inverse for skinning)
  *   mbik_plan_destroy  <- ~ManyBoneIK3D / set_dirty() rebuild
  *   mbik_last_error    <- ERR_FAIL_* messages (the reference prints and returns)
  *
@@ -50,7 +52,7 @@ extern "C" {
 #define MBIK_EUNSUPPORTED (-4)
 #define MBIK_ENODEV (-5)
 
-#define MBIK_ABI_VERSION 8
+#define MBIK_ABI_VERSION 9
 
 typedef struct mbik_plan mbik_plan;
 typedef struct mbik_group mbik_group;
@@ -318,9 +320,13 @@ int32_t mbik_plan_autotune(mbik_plan *plan, int32_t first, int32_t count, const 
  *     ~25 per pin per skeleton there, placement 2 none), must fit MBIK_MAX_LDS_BYTES; the
  *     automatic layout shrinks skeletons per block and moves state to device memory first,
  *     so only the topology tables of a very large rig (several thousand bones) hit this;
- *   - constraint_mode stages its per-lane stacks in LDS with the same limit. */
+ *   - constraint_mode stages its per-lane stacks in LDS with the same limit;
+ *   - mbik_pose_globals keeps one skeleton's poses and globals (22 floats per bone) in LDS with
+ *     the same limit: a rig may have at most MBIK_FK_MAX_BONES bones there (the solve itself
+ *     takes larger rigs). */
 #define MBIK_MAX_PATH_BONES 4096
 #define MBIK_MAX_LDS_BYTES (160 * 1024)
+#define MBIK_FK_MAX_BONES 1861
 int32_t mbik_solve(mbik_plan *plan, int32_t first, int32_t count, const float *pose_in, const float *targets,
 		float *pose_out, void *hip_stream);
 /* mbik_solve plus a per-skeleton status byte (device buffer of `count` bytes, indexed from
@@ -343,6 +349,33 @@ int32_t mbik_solve_host(mbik_plan *plan, int32_t first, int32_t count, const flo
  * [count][pins] bytes; device pointers indexed from `first`, asynchronous on hip_stream. */
 int32_t mbik_capture_targets(mbik_plan *plan, int32_t first, int32_t count, const float *skeleton_global,
 		const float *target_global, const uint8_t *visible, float *targets, void *hip_stream);
+/* The back half of a frame (ABI 9).  == Skeleton3D::get_bone_global_pose for every bone of `count`
+ * skeletons (ik_bone_3d.cpp:71 is the reference's own call), and optionally the skin transform
+ * global * bind_inverse and each pin's distance to its target.  Device buffers, asynchronous on
+ * hip_stream (the plan's first call also uploads its bone schedule, synchronously):
+ *   pose         [count][bones][10], e.g. mbik_solve's pose_out on the same stream
+ *   inv_bind     [bones][12] per rig (basis rows, origin), or NULL
+ *   globals      [count][bones][12] basis rows, then origin (the layout of `targets`), or NULL
+ *   targets      [count][pins][12]; needed for pin_distance
+ *   pin_distance [count][pins], or NULL
+ * local(b) = Basis(rotation) * diag(scale) with origin = position (gd_math.h pose_to_xform);
+ * global(b) = local(b) for a parentless bone, else global(parent) * local(b), for every bone of
+ * the skeleton, also those outside the IK bone list; globals[s][b] = global(b) * inv_bind[b] when
+ * inv_bind is given, else global(b); pin_distance[s][e] = |global(pins[e].bone).origin -
+ * targets[s][e].origin|, always from the unskinned global.  Godot's operation order, unfused
+ * (bitwise the reference's float results; mbik_pose_globals_cpu gives the same bits).
+ * Only the rig (parents in any order, pin bones) is read from the plan, no per-skeleton table:
+ * there is no `first`, and count may exceed the plan's skeleton count.  At least one of globals
+ * and pin_distance must be non-NULL, pin_distance needs targets, and pose must not overlap
+ * globals (MBIK_EINVAL).  count == 0 returns MBIK_OK without a launch; a plan without pins
+ * ignores pin_distance; non-finite values propagate.  Buffers need float alignment only (16-byte
+ * aligned ones move 16 bytes a lane).  Rigs above MBIK_FK_MAX_BONES bones: MBIK_EUNSUPPORTED. */
+int32_t mbik_pose_globals(mbik_plan *plan, int32_t count, const float *pose, const float *inv_bind,
+		float *globals, const float *targets, float *pin_distance, void *hip_stream);
+/* Host-only (no device needed, like mbik_describe_topology): the same arithmetic from the same
+ * code, host buffers, for a rig description (bone_count, parents, pins; any bone count). */
+int32_t mbik_pose_globals_cpu(const mbik_skeleton_desc *desc, int32_t count, const float *pose,
+		const float *inv_bind, float *globals, const float *targets, float *pin_distance);
 
 /* Heterogeneous batches: several plans (distinct rigs, e.g. a crowd of different characters)
  * solved by ONE launch, each plan with its own layout.  The reference runs one

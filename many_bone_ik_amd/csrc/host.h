@@ -91,6 +91,10 @@ struct mbik_plan {
 	// override of mbik_plan_debug_helper (0: kHelpTimeoutMs)
 	unsigned int *help_flag = nullptr;
 	int help_timeout_us = 0;
+	// mbik_pose_globals: the device copy of the depth-ordered bone schedule (kernels.h launch_fk), built
+	// from src_parents / src_pins on the first call and owned through allocs
+	int *d_fk_sched = nullptr;
+	int fk_levels = 0;
 };
 
 namespace mbik_host {

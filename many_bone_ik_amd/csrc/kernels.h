@@ -162,6 +162,11 @@ hipError_t launch_setup(hipStream_t st, int threads, const SetupView &v, int fir
 hipError_t launch_topology(const TopoSlice *slices, int n);
 hipError_t launch_tile_rows(hipStream_t st, const float *src, float *dst, int items, int fields, int N, int Npad);
 hipError_t launch_tile_rows(hipStream_t st, const double *src, double *dst, int items, int fields, int N, int Npad);
+// k_fk.hip: mbik_pose_globals (fk.h).  S skeletons a block, fk_lds_floats(B, S) floats of LDS; sched is the
+// device copy of the depth-ordered schedule: [levels + 1] level offsets (padded to an even count),
+// [B] (bone, parent) pairs in schedule order, [P] pin bones.
+hipError_t launch_fk(hipStream_t st, int count, int B, int P, int S, int levels, const int *sched, const float *pose,
+		const float *inv_bind, float *globals, const float *targets, float *pin_distance);
 #ifdef MBIK_PROF
 // Diagnostic cycle accounting (-DMBIK_PROF): each kernel TU has its own counters; adds them to
 // out[24] and clears them.

@@ -18,7 +18,7 @@ import math
 
 import numpy as np
 
-from .solver import Plan, describe_topology
+from .solver import Plan, describe_topology, pose_globals_cpu
 
 
 class ManyBoneIK3D:
@@ -326,6 +326,12 @@ class ManyBoneIK3D:
         """Segmentation the next plan would use (no device needed)."""
         return describe_topology(self.parents, self._pin_list(), [], iterations=self.iterations_per_frame,
                                  default_damp=self.default_damp, bone_damp=self.bone_damp or None)
+
+    def bone_global_poses(self, pose, inv_bind=None):
+        """== Skeleton3D::get_bone_global_pose for every bone of every skeleton of `pose`
+        [n][bones][10] (host, no device needed): [n][bones][12], basis rows then origin; times
+        inv_bind [bones][12] when given (the skin transforms)."""
+        return pose_globals_cpu(self.parents, [], pose, inv_bind)[0]
 
     def _bone_list_changed(self, setup_pose, cones=None, twist=None):
         """== ManyBoneIK3D::_bone_list_changed for a batch: (re)build the device plan."""

@@ -73,6 +73,27 @@ def describe_topology(parents, pins, constraints=(), *, iterations=15, default_d
     return dict(bone_list=bl[:nbl.value], seg_root=r[:ns], seg_tip=t[:ns], seg_parent=p[:ns], seg_headings=nh[:ns])
 
 
+def pose_globals_cpu(parents, pins, pose, inv_bind=None, targets=None):
+    """mbik_pose_globals_cpu (host only): skeleton-space bone transforms of `pose` [n][bones][10]
+    -- Skeleton3D::get_bone_global_pose for every bone, times inv_bind [bones][12] when given --
+    and, with `targets` [n][pins][12], each pin's distance to its target.  `pins` are bone
+    indices or pin dicts.  Returns (globals [n][bones][12], distances [n][pins] or None)."""
+    L = _lib.load()
+    pins = [p if isinstance(p, dict) else dict(bone=int(p)) for p in pins]
+    d = _Desc(parents, pins, [], 1, 15, math.radians(5.0), False, 0, None)
+    pose = np.ascontiguousarray(pose, np.float32)
+    n, B, P = pose.shape[0], d.parents.shape[0], len(pins)
+    assert pose.shape == (n, B, 10), pose.shape
+    ib = None if inv_bind is None else np.ascontiguousarray(inv_bind, np.float32)
+    assert ib is None or ib.shape == (B, 12), ib.shape
+    tg = None if targets is None else np.ascontiguousarray(targets, np.float32)
+    assert tg is None or tg.shape == (n, P, 12), tg.shape
+    out = np.empty((n, B, 12), np.float32)
+    dist = None if tg is None else np.empty((n, P), np.float32)
+    check(L.mbik_pose_globals_cpu(C.byref(d.desc), n, _ptr(pose), _ptr(ib), _ptr(out), _ptr(tg), _ptr(dist)))
+    return out, dist
+
+
 def _rig_arrays(rigs):
     """ctypes arrays of descs / configs for (parents, pins, constraints, config-kwargs) rigs;
     returns (descs, configs, keepalive)."""
@@ -301,6 +322,16 @@ class Plan:
         check(self._L.mbik_capture_targets(self.h, first, count, C.c_void_p(skeleton_global_ptr),
                                            C.c_void_p(target_global_ptr), C.c_void_p(visible_ptr or None),
                                            C.c_void_p(targets_ptr), C.c_void_p(stream or None)))
+
+    def pose_globals(self, pose_ptr: int, globals_ptr: int = 0, count: int | None = None, inv_bind_ptr: int = 0,
+                     targets_ptr: int = 0, pin_distance_ptr: int = 0, stream: int = 0):
+        """mbik_pose_globals: skeleton-space bone transforms [count][bones][12] of device poses
+        (times inv_bind [bones][12] when given) and / or pin-to-target distances [count][pins];
+        asynchronous on `stream`.  Only the rig is read from the plan: count may exceed self.n."""
+        count = self.n if count is None else count
+        check(self._L.mbik_pose_globals(self.h, count, C.c_void_p(pose_ptr or None), C.c_void_p(inv_bind_ptr or None),
+                                        C.c_void_p(globals_ptr or None), C.c_void_p(targets_ptr or None),
+                                        C.c_void_p(pin_distance_ptr or None), C.c_void_p(stream or None)))
 
     def segment_solve(self, segment: int, pose_ptr: int, targets_ptr: int, first: int = 0, count: int | None = None,
                       stream: int = 0):
