@@ -52,7 +52,7 @@ extern "C" {
 #define MBIK_EUNSUPPORTED (-4)
 #define MBIK_ENODEV (-5)
 
-#define MBIK_ABI_VERSION 9
+#define MBIK_ABI_VERSION 10
 
 typedef struct mbik_plan mbik_plan;
 typedef struct mbik_group mbik_group;
@@ -323,10 +323,13 @@ int32_t mbik_plan_autotune(mbik_plan *plan, int32_t first, int32_t count, const 
  *   - constraint_mode stages its per-lane stacks in LDS with the same limit;
  *   - mbik_pose_globals keeps one skeleton's poses and globals (22 floats per bone) in LDS with
  *     the same limit: a rig may have at most MBIK_FK_MAX_BONES bones there (the solve itself
- *     takes larger rigs). */
+ *     takes larger rigs);
+ *   - mbik_skin_vertices keeps one skeleton's skin transforms (12 floats per bone) in LDS with the
+ *     same limit: a mesh may be bound to at most MBIK_SKIN_MAX_BONES bones (mbik_mesh_create). */
 #define MBIK_MAX_PATH_BONES 4096
 #define MBIK_MAX_LDS_BYTES (160 * 1024)
 #define MBIK_FK_MAX_BONES 1861
+#define MBIK_SKIN_MAX_BONES 3413
 int32_t mbik_solve(mbik_plan *plan, int32_t first, int32_t count, const float *pose_in, const float *targets,
 		float *pose_out, void *hip_stream);
 /* mbik_solve plus a per-skeleton status byte (device buffer of `count` bytes, indexed from
@@ -376,6 +379,59 @@ int32_t mbik_pose_globals(mbik_plan *plan, int32_t count, const float *pose, con
  * code, host buffers, for a rig description (bone_count, parents, pins; any bone count). */
 int32_t mbik_pose_globals_cpu(const mbik_skeleton_desc *desc, int32_t count, const float *pose,
 		const float *inv_bind, float *globals, const float *targets, float *pin_distance);
+
+/* Linear blend skinning of a mesh from skin transforms (ABI 10): what mbik_pose_globals' skinned
+ * output exists for, on the device and on the stream of the solve.  The semantics are those of
+ * Godot's skeleton compute shader -- blend the bone matrices, then transform -- on the ArrayMesh
+ * surface arrays ARRAY_VERTEX, ARRAY_NORMAL, ARRAY_BONES and ARRAY_WEIGHTS with 4 or 8 influences
+ * a vertex.  For vertex v of skeleton s, X_k = skin[s][bone_indices[v][k]], w_k = weights[v][k]:
+ *   M = X_0 * w_0, then M = M + X_k * w_k for k = 1 .. K-1 in influence order, every element of the
+ *   12 floats and every influence, weight 0 included;
+ *   out_positions[s][v] = M * positions[v]  (per row ((r.x*v.x + r.y*v.y) + r.z*v.z) + origin);
+ *   out_normals[s][v]   = M.basis * normals[v], the same matrix without the origin, not renormalised.
+ * float32, unfused, in that order; mbik_skin_vertices_cpu is the specification (a renderer fixes no
+ * float order) and the device gives the same bits.  Weights are used as given: not normalised, not
+ * sorted, negative ones and sums other than 1 allowed.  Non-finite values propagate: a NaN in one
+ * bone's matrix reaches exactly the vertices that list that bone, also with weight 0.
+ *
+ * A mesh is its own handle, bound to a bone count and a device, not to a plan: one rig can carry
+ * several meshes and one mesh can serve several plans.  mbik_mesh_create reads host arrays --
+ *   positions    [vertex_count][3]
+ *   normals      [vertex_count][3], or NULL for a mesh without normals
+ *   bone_indices [vertex_count][influences]
+ *   weights      [vertex_count][influences]
+ * -- checks them on the host and copies them, repacked for the kernel, to `device`
+ * (synchronously).  MBIK_EINVAL: influences other than 4 or 8, a negative count, a null array of a
+ * mesh with vertices, any bone index outside [0, bone_count), a null out_mesh.
+ * MBIK_EUNSUPPORTED: bone_count above MBIK_SKIN_MAX_BONES (one skeleton's matrices, 48 bytes a
+ * bone, must fit MBIK_MAX_LDS_BYTES).  A mesh is immutable afterwards; the kernel relies on the
+ * index check made here and tests no index itself. */
+typedef struct mbik_mesh mbik_mesh;
+int32_t mbik_mesh_create(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
+		const float *normals, const int32_t *bone_indices, const float *weights, int32_t device, mbik_mesh **out_mesh);
+void mbik_mesh_destroy(mbik_mesh *mesh);
+/* Skins the mesh for `count` skeletons.  Device buffers on the mesh's device, asynchronous on
+ * hip_stream (NULL = default stream):
+ *   skin          [count][bones][12] basis rows, then origin, e.g. mbik_pose_globals' output with
+ *                 inv_bind on the same stream
+ *   out_positions [count][vertices][3]
+ *   out_normals   [count][vertices][3], or NULL
+ * MBIK_EINVAL: count < 0, a null skin or out_positions, out_normals for a mesh without normals, an
+ * output that overlaps skin or the other output.  count == 0 or a mesh without vertices returns
+ * MBIK_OK without a launch.  Buffers need float alignment only (a 16-byte aligned skin is staged
+ * 16 bytes a lane).  Element offsets are 64-bit: count x vertices x 3 may exceed 2^31. */
+int32_t mbik_skin_vertices(mbik_mesh *mesh, int32_t count, const float *skin, float *out_positions, float *out_normals,
+		void *hip_stream);
+/* Host-only (no device needed): the same arithmetic from the same code on host buffers, with
+ * mbik_mesh_create's and mbik_skin_vertices' checks (any bone count). */
+int32_t mbik_skin_vertices_cpu(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
+		const float *normals, const int32_t *bone_indices, const float *weights, int32_t count, const float *skin,
+		float *out_positions, float *out_normals);
+/* The launch shape mbik_skin_vertices would use for `count` skeletons: a block owns
+ * skeletons_per_block consecutive skeletons (their matrices in LDS) and one of vertex_chunks
+ * pieces of the vertex range; the grid is skeleton tiles x vertex chunks, so that a small count
+ * with a large mesh still fills the device.  Either output may be NULL. */
+int32_t mbik_mesh_launch_shape(const mbik_mesh *mesh, int32_t count, int32_t *skeletons_per_block, int32_t *vertex_chunks);
 
 /* Heterogeneous batches: several plans (distinct rigs, e.g. a crowd of different characters)
  * solved by ONE launch, each plan with its own layout.  The reference runs one

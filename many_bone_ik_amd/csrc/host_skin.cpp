@@ -1,0 +1,167 @@
+// Linear blend skinning of meshes from skin transforms (include/mbik.h, ABI 10): the mesh handle,
+// mbik_skin_vertices, which launches k_skin.hip's kernel on the mesh's device, and
+// mbik_skin_vertices_cpu, which runs the same per-vertex code (skin.h) on the host.  The
+// semantics are those of Godot's skeleton compute shader on ArrayMesh surface arrays;
+// DESIGN.md §14.
+#include "host.h"
+
+#include "skin.h"
+
+using namespace mbik_host;
+
+struct mbik_mesh {
+	int device = 0, cu_count = 256;
+	int32_t B = 0, V = 0, K = 4;
+	bool normals = false;
+	unsigned char *d_mesh = nullptr; // skin_layout()'s planes
+};
+
+namespace {
+
+// LDS a block aims for: eight 256-thread blocks (all 32 wave slots) share a CU's 160 KiB.
+// (-DMBIK_SKIN_LDS_TARGET_KIB=n: A/B builds of the skeletons-per-block trade-off)
+#ifndef MBIK_SKIN_LDS_TARGET_KIB
+#define MBIK_SKIN_LDS_TARGET_KIB 20
+#endif
+constexpr int64_t kSkinBlockLdsTarget = MBIK_SKIN_LDS_TARGET_KIB * 1024;
+// Skeletons a block loops over with one vertex in registers; more would amortise nothing further
+// (the mesh is read from L2) and leave fewer blocks to balance.
+constexpr int kSkinMaxSkeletonsPerBlock = 16;
+// Blocks the grid aims for before it stops splitting the vertex range: eight per CU.
+constexpr int kSkinBlocksPerCu = 8;
+
+bool overlap(const void *a, size_t na, const void *b, size_t nb) {
+	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+	return x < y + nb && y < x + na;
+}
+
+struct SkinShape {
+	int S, chunk, chunks, vshift;
+};
+
+// S: as many skeletons as the LDS target holds.  Vertex chunks: enough for kSkinBlocksPerCu blocks
+// a CU, but no chunk shorter than 256 vertices or than 8 vertices per bone -- every block stages
+// its S x B matrices again, 12 LDS dword writes a bone against 3 K quad reads a vertex.
+SkinShape shape_of(const mbik_mesh *m, int64_t count) {
+	const int64_t per = std::max<int64_t>(48, (int64_t)m->B * 48);
+	SkinShape sh;
+	sh.S = (int)std::max<int64_t>(1, std::min<int64_t>({kSkinBlockLdsTarget / per, kSkinMaxSkeletonsPerBlock, count}));
+	const int64_t tiles = std::max<int64_t>(1, (count + sh.S - 1) / sh.S);
+	const int64_t chunk_min = std::max<int64_t>(256, ((int64_t)m->B * 8 + 255) / 256 * 256);
+	const int64_t want = ((int64_t)m->cu_count * kSkinBlocksPerCu + tiles - 1) / tiles;
+	const int64_t n = std::max<int64_t>(1, std::min<int64_t>(want, m->V / chunk_min));
+	sh.chunk = (int)std::max<int64_t>(256, ((m->V + n - 1) / n + 255) / 256 * 256);
+	sh.chunks = (int)std::max<int64_t>(1, ((int64_t)m->V + sh.chunk - 1) / sh.chunk);
+	const int lanes = std::min<int64_t>(sh.chunk, m->V);
+	sh.vshift = lanes <= 64 ? 6 : (lanes <= 128 ? 7 : 8);
+	return sh;
+}
+
+int check_mesh(int32_t B, int32_t V, int32_t K, const float *positions, const int32_t *bone_indices, const float *weights) {
+	int64_t bad_v = 0;
+	int bad_k = 0;
+	const mbik::SkinCheck c = mbik::skin_check_mesh(B, V, K, positions, bone_indices, weights, &bad_v, &bad_k);
+	if (c == mbik::SKIN_BAD_INDEX)
+		return fail(MBIK_EINVAL, "vertex " + std::to_string(bad_v) + " influence " + std::to_string(bad_k) + ": bone index " +
+				std::to_string(bone_indices[bad_v * K + bad_k]) + " outside [0, " + std::to_string(B) + ")");
+	if (c != mbik::SKIN_OK) return fail(MBIK_EINVAL, mbik::skin_check_text(c));
+	return MBIK_OK;
+}
+
+// The argument checks of a skinning call past the mesh's own; 0 = launch, 1 = nothing to do.
+int check_call(int32_t B, int32_t V, bool mesh_normals, int32_t count, const float *skin, const float *out_positions,
+		const float *out_normals) {
+	if (count < 0) return fail(MBIK_EINVAL, "negative count");
+	if (out_normals && !mesh_normals) return fail(MBIK_EINVAL, "out_normals given for a mesh without normals");
+	if (count == 0 || V == 0) return 1;
+	if (!skin) return fail(MBIK_EINVAL, "null skin");
+	if (!out_positions) return fail(MBIK_EINVAL, "null out_positions");
+	const size_t nskin = (size_t)count * B * 12 * sizeof(float), nout = (size_t)count * V * 3 * sizeof(float);
+	if (overlap(skin, nskin, out_positions, nout)) return fail(MBIK_EINVAL, "out_positions overlaps skin");
+	if (out_normals && overlap(skin, nskin, out_normals, nout)) return fail(MBIK_EINVAL, "out_normals overlaps skin");
+	if (out_normals && overlap(out_positions, nout, out_normals, nout)) return fail(MBIK_EINVAL, "out_normals overlaps out_positions");
+	return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t mbik_mesh_create(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions, const float *normals,
+		const int32_t *bone_indices, const float *weights, int32_t device, mbik_mesh **out_mesh) {
+	if (!out_mesh) return fail(MBIK_EINVAL, "null out_mesh");
+	*out_mesh = nullptr;
+	if (influences != 4 && influences != 8) return fail(MBIK_EINVAL, mbik::skin_check_text(mbik::SKIN_BAD_INFLUENCES));
+	if (bone_count < 0 || vertex_count < 0) return fail(MBIK_EINVAL, mbik::skin_check_text(mbik::SKIN_NEGATIVE));
+	if (vertex_count > 0 && (!positions || !bone_indices || !weights)) return fail(MBIK_EINVAL, mbik::skin_check_text(mbik::SKIN_NULL));
+	if (bone_count > mbik::kSkinMaxBones)
+		return fail(MBIK_EUNSUPPORTED, "rig has " + std::to_string(bone_count) + " bones; a mesh supports at most " +
+				std::to_string(mbik::kSkinMaxBones) + " (MBIK_SKIN_MAX_BONES: one skeleton's matrices must fit 160 KiB of LDS)");
+	if (int rc = check_mesh(bone_count, vertex_count, influences, positions, bone_indices, weights)) return rc;
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MBIK_ENODEV, "no HIP device visible");
+	if (device < 0 || device >= ndev) return fail(MBIK_EINVAL, "device index out of range");
+	std::unique_ptr<mbik_mesh> m(new mbik_mesh());
+	m->device = device, m->B = bone_count, m->V = vertex_count, m->K = influences, m->normals = normals != nullptr;
+	DeviceGuard guard(device);
+	int cus = 0;
+	if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) m->cu_count = cus;
+	if (vertex_count > 0) {
+		const mbik::SkinLayout l = mbik::skin_layout(vertex_count, influences, m->normals);
+		std::vector<unsigned char> packed((size_t)l.bytes);
+		mbik::skin_pack(vertex_count, influences, positions, normals, bone_indices, weights, packed.data());
+		void *d = nullptr;
+		if (hipMalloc(&d, packed.size()) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc failed for the mesh");
+		m->d_mesh = static_cast<unsigned char *>(d);
+		if (hipMemcpy(d, packed.data(), packed.size(), hipMemcpyHostToDevice) != hipSuccess) {
+			(void)hipFree(d);
+			return fail(MBIK_EHIP, "hipMemcpy failed for the mesh");
+		}
+	}
+	*out_mesh = m.release();
+	return MBIK_OK;
+}
+
+void mbik_mesh_destroy(mbik_mesh *m) {
+	if (!m) return;
+	if (m->d_mesh) {
+		DeviceGuard guard(m->device);
+		(void)hipFree(m->d_mesh);
+	}
+	delete m;
+}
+
+int32_t mbik_mesh_launch_shape(const mbik_mesh *m, int32_t count, int32_t *skeletons_per_block, int32_t *vertex_chunks) {
+	if (!m) return fail(MBIK_EINVAL, "null mesh");
+	if (count < 0) return fail(MBIK_EINVAL, "negative count");
+	const SkinShape sh = shape_of(m, count);
+	if (skeletons_per_block) *skeletons_per_block = sh.S;
+	if (vertex_chunks) *vertex_chunks = sh.chunks;
+	return MBIK_OK;
+}
+
+int32_t mbik_skin_vertices(mbik_mesh *m, int32_t count, const float *skin, float *out_positions, float *out_normals,
+		void *hip_stream) {
+	if (!m) return fail(MBIK_EINVAL, "null mesh");
+	const int rc = check_call(m->B, m->V, m->normals, count, skin, out_positions, out_normals);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	DeviceGuard guard(m->device);
+	const SkinShape sh = shape_of(m, count);
+	hipError_t e = mbik::launch_skin(reinterpret_cast<hipStream_t>(hip_stream), m->K, count, m->B, m->V, sh.S, sh.chunk, sh.chunks,
+			sh.vshift, m->d_mesh, m->normals, skin, out_positions, out_normals);
+	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("skinning launch failed: ") + hipGetErrorString(e));
+	return MBIK_OK;
+}
+
+int32_t mbik_skin_vertices_cpu(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
+		const float *normals, const int32_t *bone_indices, const float *weights, int32_t count, const float *skin,
+		float *out_positions, float *out_normals) {
+	if (int rc = check_mesh(bone_count, vertex_count, influences, positions, bone_indices, weights)) return rc;
+	const int rc = check_call(bone_count, vertex_count, normals != nullptr, count, skin, out_positions, out_normals);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	mbik::skin_vertices_host(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, count, skin,
+			out_positions, out_normals);
+	return MBIK_OK;
+}
+
+} // extern "C"

@@ -9,42 +9,15 @@
 // cover the (skeleton, bone of the level) pairs, read the parent's global from LDS and meet at
 // one block barrier per level.
 #include <mutex>
-#include <type_traits>
 
 #include "fk.h"
 #include "kernels.h"
+#include "lds_copy.h"
 
 namespace {
 using namespace mbik;
 
 constexpr int kFkThreads = 256;
-
-// run r (of `runs`, `len` floats each) lies at g + r * len in device memory and at l + r * lstride
-// in LDS.  With several runs len is a multiple of 4, so every run has the head of the first.
-template <bool TO_LDS>
-__device__ __forceinline__ void fk_copy_runs(float *l, int lstride, typename std::conditional<TO_LDS, const float, float>::type *g,
-		int len, int runs) {
-	const int mis = (int)((reinterpret_cast<uintptr_t>(g) >> 2) & 3); // floats past a 16-byte boundary
-	const int head = min(len, (4 - mis) & 3);
-	const int nvec = (len - head) >> 2;
-	const int edge = len - 4 * nvec; // head + tail floats of a run
-	for (int i = threadIdx.x; i < runs * nvec; i += kFkThreads) {
-		const int r = i / nvec, k = head + 4 * (i - r * nvec);
-		float *lp = l + r * lstride + k;
-		if constexpr (TO_LDS) {
-			const float4 v = *reinterpret_cast<const float4 *>(g + (size_t)r * len + k);
-			lp[0] = v.x, lp[1] = v.y, lp[2] = v.z, lp[3] = v.w;
-		} else {
-			*reinterpret_cast<float4 *>(g + (size_t)r * len + k) = make_float4(lp[0], lp[1], lp[2], lp[3]);
-		}
-	}
-	for (int i = threadIdx.x; i < runs * edge; i += kFkThreads) {
-		const int r = i / edge, j = i - r * edge;
-		const int k = j < head ? j : j + 4 * nvec;
-		if constexpr (TO_LDS) l[r * lstride + k] = g[(size_t)r * len + k];
-		else g[(size_t)r * len + k] = l[r * lstride + k];
-	}
-}
 
 // sched: [levels + 1] level offsets, then [B] (bone, parent) pairs in schedule order, then [P] pin bones.
 __global__ __launch_bounds__(kFkThreads) void mbik_fk_kernel(int count, int B, int P, int S, int levels,
@@ -61,7 +34,7 @@ __global__ __launch_bounds__(kFkThreads) void mbik_fk_kernel(int count, int B, i
 	const int2 *pairs = reinterpret_cast<const int2 *>(sched + levels + 1 + ((levels + 1) & 1));
 	const int *pin_bone = reinterpret_cast<const int *>(pairs + B);
 
-	fk_copy_runs<true>(Pl, 0, pose + s0 * B * 10, ns * B * 10, 1);
+	lds_copy_runs<true, kFkThreads>(Pl, 0, pose + s0 * B * 10, ns * B * 10, 1);
 	__syncthreads();
 	// locals of every (skeleton, bone); the roots' are their globals
 	for (int i = threadIdx.x; i < ns * B; i += kFkThreads) {
@@ -94,7 +67,7 @@ __global__ __launch_bounds__(kFkThreads) void mbik_fk_kernel(int count, int B, i
 		}
 		__syncthreads();
 	}
-	fk_copy_runs<false>(G, gs, globals + s0 * B * 12, B * 12, ns);
+	lds_copy_runs<false, kFkThreads>(G, gs, globals + s0 * B * 12, B * 12, ns);
 }
 } // namespace
 

@@ -167,6 +167,11 @@ hipError_t launch_tile_rows(hipStream_t st, const double *src, double *dst, int 
 // [B] (bone, parent) pairs in schedule order, [P] pin bones.
 hipError_t launch_fk(hipStream_t st, int count, int B, int P, int S, int levels, const int *sched, const float *pose,
 		const float *inv_bind, float *globals, const float *targets, float *pin_distance);
+// k_skin.hip: mbik_skin_vertices (skin.h).  Grid = ceil(count / S) skeleton tiles x `chunks` vertex chunks of `chunk`
+// vertices; S * B * 48 bytes of LDS a block; the block's 256 threads are (1 << vshift) vertex lanes (64, 128 or 256)
+// by 256 >> vshift skeleton groups.  mesh is the device copy in skin_layout()'s planes; out_n null = positions only.
+hipError_t launch_skin(hipStream_t st, int K, int count, int B, int V, int S, int chunk, int chunks, int vshift,
+		const unsigned char *mesh, bool mesh_normals, const float *skin, float *out_p, float *out_n);
 #ifdef MBIK_PROF
 // Diagnostic cycle accounting (-DMBIK_PROF): each kernel TU has its own counters; adds them to
 // out[24] and clears them.
