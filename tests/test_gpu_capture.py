@@ -48,6 +48,46 @@ def test_capture_matches_oracle(oracle, mbik, torch_dev):
             assert np.array_equal(got[s, e].view(np.uint32), want.view(np.uint32)), (s, e)
 
 
+def test_capture_subrange_keeps_everything_else(oracle, mbik, torch_dev):
+    """Range [15, 33) of 83 skeletons, every buffer indexed from skeleton 15 and carrying 64 guard
+    rows on each side: hidden pins sit inside the range and at both of its ends; rows outside the
+    range and hidden entries keep their previous bits; skeleton_global and target_global are NaN
+    outside the range, so a read from a wrong row cannot give the oracle's bits."""
+    torch, dev = torch_dev
+    rng = np.random.default_rng(9)
+    n, a, c, G = 83, 15, 18, 64
+    wl = W.generate(2, n)
+    plan = Plan.from_workload(wl)
+    P = wl.targets.shape[1]
+    rows, lo, hi = G + n + G, G + a, G + a + c
+    skel = np.full((rows, 12), np.nan, np.float32)
+    node = np.full((rows, P, 12), np.nan, np.float32)
+    skel[lo:hi] = random_xforms(rng, (c,))
+    node[lo:hi] = random_xforms(rng, (c, P))
+    visible = np.ones((rows, P), np.uint8)          # (a wrongly captured row outside the range would turn NaN)
+    hidden = [(a, 0), (a, P - 1), (a + 7, 1), (a + c - 1, 0), (a + c - 1, P - 1)]
+    for s, e in hidden:
+        visible[G + s, e] = 0
+    prev = random_xforms(rng, (rows, P), scale=False)
+    d_skel, d_node = torch.from_numpy(skel).to(dev), torch.from_numpy(node).to(dev)
+    d_vis, d_tg = torch.from_numpy(visible).to(dev), torch.from_numpy(prev.copy()).to(dev)
+    plan.capture_targets(d_skel[lo].data_ptr(), d_node[lo].data_ptr(), d_tg[lo].data_ptr(), d_vis[lo].data_ptr(), first=a, count=c)
+    torch.cuda.synchronize()
+    got = d_tg.cpu().numpy()
+    want = prev.copy()
+    for s in range(lo, hi):
+        inv = oracle.xform_affine_inverse(skel[s])
+        for e in range(P):
+            if visible[s, e]:
+                want[s, e] = oracle.xform_mul(inv, node[s, e])
+    assert not np.isnan(want).any()
+    diff = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
+    assert diff.size == 0, f"{len(diff)} values differ; first (row - {G}, pin, float) {(diff[:5] - [G, 0, 0]).tolist()}"
+    for t, h in ((d_skel, skel), (d_node, node)):
+        assert np.array_equal(t.cpu().numpy().view(np.uint32), h.view(np.uint32))
+    assert np.array_equal(d_vis.cpu().numpy(), visible)
+
+
 def test_capture_then_solve(oracle, mbik, torch_dev):
     """Scene-space targets -> capture -> solve == the oracle solving the captured targets."""
     torch, dev = torch_dev

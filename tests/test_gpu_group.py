@@ -65,8 +65,8 @@ def test_group_subranges_and_repeat(oracle, mbik, torch_dev):
         if c == 0:
             assert torch.isnan(o).all()     # untouched
             continue
-        ref = p.solve_host(wl.pose[f:f + c], wl.targets[f:f + c], first=f)
-        assert_parity(o.cpu().numpy(), ref, f"{wl.topo.name} [{f}, {f + c})")
+        ref = oracle.Oracle(wl).solve(wl.pose, wl.targets, threads=4)[f:f + c]
+        assert_parity(o.cpu().numpy(), np.ascontiguousarray(ref), f"{wl.topo.name} [{f}, {f + c})")
     g.close()
 
 
