@@ -19,6 +19,8 @@
  *                         (one call = one segment_solver() of one segment subtree)
  *   mbik_pose_globals  <- Skeleton3D::get_bone_global_pose for every bone, as the reference calls
  *                         it at src/ik_bone_3d.cpp:71 (and global * bind_inverse for skinning)
+ *   mbik_pose_blend    <- Skeleton3D::_process_modifiers' blend of the poses before and after a
+ *                         SkeletonModifier3D by its inherited `influence` property (Godot 4.3 core)
  *   mbik_plan_destroy  <- ~ManyBoneIK3D / set_dirty() rebuild
  *   mbik_last_error    <- ERR_FAIL_* messages (the reference prints and returns)
  *
@@ -52,7 +54,7 @@ extern "C" {
 #define MBIK_EUNSUPPORTED (-4)
 #define MBIK_ENODEV (-5)
 
-#define MBIK_ABI_VERSION 10
+#define MBIK_ABI_VERSION 11
 
 typedef struct mbik_plan mbik_plan;
 typedef struct mbik_group mbik_group;
@@ -379,6 +381,46 @@ int32_t mbik_pose_globals(mbik_plan *plan, int32_t count, const float *pose, con
  * code, host buffers, for a rig description (bone_count, parents, pins; any bone count). */
 int32_t mbik_pose_globals_cpu(const mbik_skeleton_desc *desc, int32_t count, const float *pose,
 		const float *inv_bind, float *globals, const float *targets, float *pin_distance);
+
+/* Modifier influence (ABI 11): ManyBoneIK3D is a SkeletonModifier3D, and Godot 4.3's
+ * Skeleton3D::_process_modifiers blends every bone's pose from before the modifier with the
+ * modifier's by the inherited `influence` property.  mbik_solve is _process_modification alone;
+ * this is that blend, on the device and on the stream of the solve, between mbik_solve and
+ * mbik_pose_globals.  Device buffers, asynchronous on hip_stream:
+ *   pose_in   [count][bones][10] the poses the modifier was given (mbik_solve's pose_in)
+ *   pose_mod  [count][bones][10] the modifier's result (mbik_solve's pose_out)
+ *   influence the weight of every skeleton, unless
+ *   influence_per_skeleton [count] is given (device memory, read by the kernel, never by the host)
+ *   pose_out  [count][bones][10]
+ * Per bone, a = pose_in[s][b], m = pose_mod[s][b], w the skeleton's weight; float32, unfused:
+ *   1. !(w < 1), i.e. w >= 1 or NaN: out = m, the same bits (Godot does not blend).
+ *   2. A = Basis(a.rotation) * diag(a.scale) with origin a.position (Skeleton3D::get_bone_pose), M
+ *      likewise; when all 12 floats compare equal (+0 == -0, NaN != NaN): out = m, the same bits
+ *      (_process_modifiers' "avoid unneeded calculation"; q against -q takes this path).
+ *   3. A negative w (not -0) counts as 0.  The one deviation: the property's range is 0..1 and
+ *      Godot would extrapolate.
+ *   4. Transform3D::interpolate_with: sa = A.basis.get_scale(), qa = A.basis.
+ *      get_rotation_quaternion(), sm and qm from M; q = qa.slerp(qm, w).normalized()
+ *      (Quaternion::slerp: a double sine over a float one for the start's coefficient),
+ *      sc = sa.lerp(sm, w), o = A.origin.lerp(M.origin, w) (Vector3::lerp: a + (b - a) * w),
+ *      T.basis.set_quaternion_scale(q, sc).
+ *   5. Skeleton3D::set_bone_pose: out.rotation = T.basis.get_rotation_quaternion(), out.scale =
+ *      T.basis.get_scale(), out.position = o.
+ * w = 0 runs 4 and 5 like any weight: the result is the round-tripped input, as in Godot.
+ * Non-finite values propagate; a NaN result of 4 and 5 is written as the quiet NaN 0x7fc00000.
+ * mbik_pose_blend_cpu gives the same bits, and on finite poses the bits of that sequence on a
+ * host with the plan's libm_variant.
+ * Only the device, the bone count and libm_variant are read from the plan: there is no `first`,
+ * count may exceed the plan's skeleton count, and every bone of the skeleton is blended.
+ * pose_out may be exactly pose_mod or exactly pose_in (in place); any other overlap of pose_out
+ * with an input, a null pose pointer or a negative count is MBIK_EINVAL.  count == 0 returns
+ * MBIK_OK without a launch.  Buffers need float alignment only; element offsets are 64-bit. */
+int32_t mbik_pose_blend(mbik_plan *plan, int32_t count, const float *pose_in, const float *pose_mod, float influence,
+		const float *influence_per_skeleton, float *pose_out, void *hip_stream);
+/* Host-only (no device needed): the same arithmetic from the same code on host buffers, for any
+ * bone count; libm_variant is MBIK_LIBM_VARIANT_* (MBIK_EINVAL otherwise). */
+int32_t mbik_pose_blend_cpu(int32_t bone_count, int32_t libm_variant, int32_t count, const float *pose_in,
+		const float *pose_mod, float influence, const float *influence_per_skeleton, float *pose_out);
 
 /* Linear blend skinning of a mesh from skin transforms (ABI 10): what mbik_pose_globals' skinned
  * output exists for, on the device and on the stream of the solve.  The semantics are those of

@@ -367,7 +367,9 @@ GDI float acos_f(float x) { return glibc::acosf(x); }
 // round to the same float, that float is the result.  Otherwise -- essentially never -- the
 // device's own double sin and division run.  mbik_selftest_libm's SLERP_SCALE0 class compares
 // the result with the host glibc's for all 2^32 omega.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MBIK_EXACT_SLERP_SIN)
+// sin(x) by its odd Taylor polynomial through x^21, for |x| <= 1.6 (truncation < 2^-58, evaluation
+// < 2^-50 relative).  Double fma and * only, every one IEEE-exact, so the host and the device
+// compute the same bits: blend.h's general-weight slerp runs it on both sides.
 GDI double sin_taylor(double x) {
 	const double x2 = x * x;
 	double p = 0x1.71b8ef6dcf572p-66;        //  1/21!
@@ -382,6 +384,7 @@ GDI double sin_taylor(double x) {
 	p = fma(p, x2, -0x1.5555555555555p-3);   // -1/3!
 	return fma(x * x2, p, x);
 }
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(MBIK_EXACT_SLERP_SIN)
 GDI float slerp_scale0(float omega, int lv = LIBM_FMA) {
 	if (fabsf(omega) <= 1.6f) {
 		const float sinom = lv == LIBM_SSE2 ? glibc::sinf_small<false>(omega) : glibc::sinf_small<true>(omega);

@@ -172,6 +172,10 @@ hipError_t launch_fk(hipStream_t st, int count, int B, int P, int S, int levels,
 // by 256 >> vshift skeleton groups.  mesh is the device copy in skin_layout()'s planes; out_n null = positions only.
 hipError_t launch_skin(hipStream_t st, int K, int count, int B, int V, int S, int chunk, int chunks, int vshift,
 		const unsigned char *mesh, bool mesh_normals, const float *skin, float *out_p, float *out_n);
+// k_blend.hip: mbik_pose_blend (blend.h).  One thread per bone of the total_bones = count * B, 256 bones a block, 20 KiB
+// of static LDS; influence_per_skeleton (device, [count]) overrides influence when given; pose_out may be pose_in or pose_mod.
+hipError_t launch_blend(hipStream_t st, int64_t total_bones, int B, int libm, float influence, const float *influence_per_skeleton,
+		const float *pose_in, const float *pose_mod, float *pose_out);
 #ifdef MBIK_PROF
 // Diagnostic cycle accounting (-DMBIK_PROF): each kernel TU has its own counters; adds them to
 // out[24] and clears them.

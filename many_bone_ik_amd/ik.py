@@ -18,7 +18,7 @@ import math
 
 import numpy as np
 
-from .solver import Plan, describe_topology, pose_globals_cpu
+from .solver import Plan, describe_topology, pose_blend_cpu, pose_globals_cpu
 
 
 class ManyBoneIK3D:
@@ -33,6 +33,9 @@ class ManyBoneIK3D:
         self.constraint_mode = False
         self.stabilization_passes = 0
         self.bone_damp: list[float] = []
+        # SkeletonModifier3D's inherited properties (Godot 4.3 skeleton_modifier_3d.h)
+        self.influence = 1.0
+        self.active = True
         # pins: IKEffectorTemplate3D defaults (ik_effector_template_3d.h:40-47)
         self._pins: list[dict] = []
         self._pin_count = 0          # pin_count: set_pin_count changes it without resizing pins (:58-60)
@@ -291,6 +294,19 @@ class ManyBoneIK3D:
     def get_stabilization_passes(self):
         return self.stabilization_passes
 
+    # ----------------------------------------------------------------- SkeletonModifier3D
+    def set_influence(self, influence: float):            # applied by Skeleton3D::_process_modifiers
+        self.influence = float(influence)
+
+    def get_influence(self) -> float:
+        return self.influence
+
+    def set_active(self, active: bool):
+        self.active = bool(active)
+
+    def is_active(self) -> bool:
+        return self.active
+
     # ----------------------------------------------------------------- plan / solve
     def _pin_list(self):
         """Pins whose bone name resolves, in pin order (an unnamed or unknown-bone pin gets no
@@ -356,8 +372,18 @@ class ManyBoneIK3D:
         index of get_pin_count()'s list, as each IKEffector3D reads its own target node.  Rows
         of pins whose bone does not resolve are ignored.  The plan is rebuilt from pose_in when
         dirty, exactly when the reference calls _bone_list_changed.
+
+        As Skeleton3D::_process_modifiers does around the call: an inactive modifier leaves the
+        poses as they are, and with influence < 1 every bone is pose_in.interpolate_with(solved,
+        influence) (solver.pose_blend_cpu).
         """
         pose_in = np.ascontiguousarray(pose_in, np.float32)
+        if not self.active:
+            return pose_in.copy()
+        out = self._process_modification(pose_in, targets, cones, twist)
+        return pose_blend_cpu(pose_in, out, self.influence) if self.influence < 1.0 else out
+
+    def _process_modification(self, pose_in, targets, cones, twist):
         if self.get_effector_count() == 0 or not self._pins:   # :649-651 and the has_pins check (:669-678)
             return pose_in.copy()
         targets = np.asarray(targets, np.float32)

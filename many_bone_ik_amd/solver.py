@@ -94,6 +94,26 @@ def pose_globals_cpu(parents, pins, pose, inv_bind=None, targets=None):
     return out, dist
 
 
+def pose_blend_cpu(pose_in, pose_mod, influence, libm_variant: int = 0):
+    """mbik_pose_blend_cpu (host only): the modifier influence of Skeleton3D::_process_modifiers --
+    per bone, pose_in.interpolate_with(pose_mod, influence) written back with set_bone_pose -- for
+    poses [n][bones][10].  `influence` is a scalar or an [n] array (one weight per skeleton).
+    Returns the blended poses [n][bones][10]."""
+    L = _lib.load()
+    pose_in = np.ascontiguousarray(pose_in, np.float32)
+    pose_mod = np.ascontiguousarray(pose_mod, np.float32)
+    assert pose_in.ndim == 3 and pose_in.shape[2] == 10 and pose_mod.shape == pose_in.shape, (pose_in.shape, pose_mod.shape)
+    n, B = pose_in.shape[:2]
+    per = None
+    if np.ndim(influence) != 0:
+        per = np.ascontiguousarray(influence, np.float32)
+        assert per.shape == (n,), per.shape
+    out = np.empty_like(pose_in)
+    check(L.mbik_pose_blend_cpu(B, int(libm_variant), n, _ptr(pose_in), _ptr(pose_mod), 1.0 if per is not None else float(influence),
+                                _ptr(per), _ptr(out)))
+    return out
+
+
 def _rig_arrays(rigs):
     """ctypes arrays of descs / configs for (parents, pins, constraints, config-kwargs) rigs;
     returns (descs, configs, keepalive)."""
@@ -332,6 +352,17 @@ class Plan:
         check(self._L.mbik_pose_globals(self.h, count, C.c_void_p(pose_ptr or None), C.c_void_p(inv_bind_ptr or None),
                                         C.c_void_p(globals_ptr or None), C.c_void_p(targets_ptr or None),
                                         C.c_void_p(pin_distance_ptr or None), C.c_void_p(stream or None)))
+
+    def pose_blend(self, pose_in_ptr: int, pose_mod_ptr: int, pose_out_ptr: int, count: int | None = None,
+                   influence: float = 1.0, influence_ptr: int | None = None, stream: int | None = None):
+        """mbik_pose_blend: the modifier influence between solve() and pose_globals() -- pose_out =
+        pose_in blended towards pose_mod (the solve's output) by `influence`, or by the device
+        array influence_ptr [count] of one weight per skeleton; asynchronous on `stream`.  pose_out
+        may be pose_mod or pose_in.  Only the rig is read from the plan: count may exceed self.n."""
+        count = self.n if count is None else count
+        check(self._L.mbik_pose_blend(self.h, count, C.c_void_p(pose_in_ptr or None), C.c_void_p(pose_mod_ptr or None),
+                                      float(influence), C.c_void_p(influence_ptr or None), C.c_void_p(pose_out_ptr or None),
+                                      C.c_void_p(stream or None)))
 
     def segment_solve(self, segment: int, pose_ptr: int, targets_ptr: int, first: int = 0, count: int | None = None,
                       stream: int = 0):
