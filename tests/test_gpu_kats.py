@@ -10,7 +10,9 @@ affine inverse.  Each result must meet the KAT's expectation within CMP_EPSILON 
 oracle bit for bit; so must both normalization forms of the kernel builds.  The KAT family
 get_closest_path_point (test_ik_kusudama_3d.h:158-202) has no device counterpart: it serves
 IKKusudama3D::local_point_on_path_sequence (ik_kusudama_3d.cpp:235-258), which the solve never
-calls.  Needs an MI355X: -m gpu."""
+calls.  What the random QCP and cone cases mean geometrically (a Kabsch rotation, the nearest
+point of the allowed region) is checked in tests/test_gpu_geometry.py against float64 models.
+Needs an MI355X: -m gpu."""
 import ctypes as C
 import json
 import math
