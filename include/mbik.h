@@ -21,6 +21,9 @@
  *                         it at src/ik_bone_3d.cpp:71 (and global * bind_inverse for skinning)
  *   mbik_pose_blend    <- Skeleton3D::_process_modifiers' blend of the poses before and after a
  *                         SkeletonModifier3D by its inherited `influence` property (Godot 4.3 core)
+ *   mbik_clip_sample   <- Animation::position_track_interpolate / rotation_track_interpolate /
+ *                         scale_track_interpolate for every bone: the animation that writes the poses
+ *                         a SkeletonModifier3D receives (Godot 4.3 core)
  *   mbik_plan_destroy  <- ~ManyBoneIK3D / set_dirty() rebuild
  *   mbik_last_error    <- ERR_FAIL_* messages (the reference prints and returns)
  *
@@ -54,7 +57,7 @@ extern "C" {
 #define MBIK_EUNSUPPORTED (-4)
 #define MBIK_ENODEV (-5)
 
-#define MBIK_ABI_VERSION 11
+#define MBIK_ABI_VERSION 12
 
 typedef struct mbik_plan mbik_plan;
 typedef struct mbik_group mbik_group;
@@ -421,6 +424,80 @@ int32_t mbik_pose_blend(mbik_plan *plan, int32_t count, const float *pose_in, co
  * bone count; libm_variant is MBIK_LIBM_VARIANT_* (MBIK_EINVAL otherwise). */
 int32_t mbik_pose_blend_cpu(int32_t bone_count, int32_t libm_variant, int32_t count, const float *pose_in,
 		const float *pose_mod, float influence, const float *influence_per_skeleton, float *pose_out);
+
+/* Animation clip sampling (ABI 12): the front stage of a frame.  In Godot the poses a
+ * SkeletonModifier3D receives were written by an animation; in a crowd each character plays its
+ * own clip at its own time.  A clip set holds several clips for one rig, resident on one device,
+ * shared by every skeleton; mbik_clip_sample writes mbik_solve's pose_in on the solve's stream from
+ * one time and one clip index per skeleton (12 bytes a skeleton instead of 40 bytes a bone).
+ *
+ * A set is its own handle, bound to a bone count, a device and a libm_variant, not to a plan (as
+ * mbik_mesh is).  mbik_clipset_create reads host arrays, checks them and uploads a repacked copy
+ * synchronously; a set is immutable afterwards.  A track holds the keys of one channel of one
+ * bone; a (bone, channel) without keys is untracked and samples to the rest pose.  MBIK_EINVAL: a
+ * null `out`, rest_pose or clips; a negative count; clip_count == 0; an unknown libm_variant,
+ * channel, interpolation or loop mode; a bone outside [0, bone_count); two tracks with keys for
+ * the same (bone, channel) in one clip; a length that is not finite or not positive; key times
+ * that are not strictly increasing, not finite or outside [0, length]; a null times or values with
+ * key_count > 0.  The kernel relies on these checks and tests no key index itself.
+ *
+ * Semantics -- Godot 4.3's Animation::_interpolate for INTERPOLATION_NEAREST / INTERPOLATION_LINEAR,
+ * LOOP_NONE / LOOP_LINEAR, forward playback, every key's transition 1.  Per skeleton s, t = time[s],
+ * C = the clip clip_index[s] (or `clip` when clip_index is NULL):
+ *   1. clip_index[s] outside [0, clip_count): every float of the skeleton is the quiet NaN
+ *      0x7fc00000; no table is read.
+ *   2. t not finite: every tracked channel is 0x7fc00000, no key is read; untracked channels as 4.
+ *   3. t' (double): LOOP_NONE t' = t < 0 ? 0 : (t > length ? length : t); LOOP_LINEAR t' =
+ *      fposmod(t, length): v = fmod(t, length); if (v < 0) v += length; v += 0.0.
+ *   4. An untracked channel: the rest pose's bits for that bone and channel.
+ *   5. A tracked channel with key times T[0..n-1], values V, wrap = (loop_mode linear && loop_wrap):
+ *      i = the last key with T[i] <= t' (exact double compare), -1 if none.  n == 1: V[0].  Not
+ *      wrap: i < 0 gives V[0], i == n-1 gives V[n-1], otherwise a = i, b = i+1, delta =
+ *      (float)(T[b] - T[a]), from = (float)(t' - T[a]).  wrap: interior i as above; i == n-1: a = n-1,
+ *      b = 0, delta = (float)((length - T[a]) + T[0]), from = (float)(t' - T[a]); i < 0: a = n-1,
+ *      b = 0, end = length - T[a], delta = (float)(end + T[0]), from = (float)(end + t').  Sums and
+ *      differences in double, rounded once.  c = |delta| < CMP_EPSILON (1e-5) ? 0 : from / delta
+ *      (IEEE float division).  Nearest: V[a].  Linear position / scale: V[a] + (V[b] - V[a]) * c
+ *      (Vector3::lerp), float32, unfused.  Linear rotation: Quaternion::slerp(V[a], V[b], c) as in
+ *      mbik_pose_blend, not renormalised; key quaternions are used as given.
+ *   6. A NaN produced by the arithmetic of 5 is stored as 0x7fc00000; copied bits stay as they are.
+ * mbik_clip_sample_cpu gives the same bits from the same code.  Deviations from Godot: _find treats
+ * a time within is_equal_approx of a key as that key, here the compare is exact; cubic
+ * interpolation, ping-pong, backward playback, key transitions (ease) and AnimationMixer's blend of
+ * several animations are not covered -- two mbik_clip_sample calls and mbik_pose_blend with a
+ * per-skeleton weight give a cross-fade. */
+typedef struct mbik_clip_track {
+	int32_t bone;            /* [0, bone_count) */
+	int32_t channel;         /* 0 position (3 floats a key), 1 rotation (4: x,y,z,w), 2 scale (3) */
+	int32_t interpolation;   /* 0 nearest, 1 linear */
+	int32_t loop_wrap;       /* Animation track loop_wrap */
+	int32_t key_count;       /* 0 allowed: same as no track */
+	const double *times;     /* [key_count] seconds, strictly increasing, finite, in [0, length] */
+	const float *values;     /* [key_count][3 or 4] */
+} mbik_clip_track;
+typedef struct mbik_clip_desc {
+	double length;           /* > 0, finite */
+	int32_t loop_mode;       /* 0 none, 1 linear */
+	int32_t track_count;
+	const mbik_clip_track *tracks;
+} mbik_clip_desc;
+typedef struct mbik_clipset mbik_clipset;
+int32_t mbik_clipset_create(int32_t bone_count, const float *rest_pose /* [bones][10] */, int32_t clip_count,
+		const mbik_clip_desc *clips, int32_t libm_variant, int32_t device, mbik_clipset **out);
+void mbik_clipset_destroy(mbik_clipset *set);
+/* Samples the set for `count` skeletons into pose_out [count][bones][10], the layout mbik_solve
+ * reads.  Device buffers on the set's device, asynchronous on hip_stream (NULL = default stream);
+ * time and clip_index are read by the kernel only, never by the host.  count == 0 or a set without
+ * bones returns MBIK_OK without a launch.  MBIK_EINVAL: a null time or pose_out, a negative count,
+ * or (with clip_index NULL) a `clip` outside the set.  Buffers need natural alignment only (float
+ * for pose_out, 8 bytes for time); element offsets are 64-bit. */
+int32_t mbik_clip_sample(mbik_clipset *set, int32_t count, const double *time /* device [count] */,
+		const int32_t *clip_index /* device [count], or NULL */, int32_t clip /* used when clip_index is NULL */,
+		float *pose_out /* device [count][bones][10] */, void *hip_stream);
+/* Host-only (no device needed): the same arithmetic from the same code on host buffers, with
+ * mbik_clipset_create's and mbik_clip_sample's checks. */
+int32_t mbik_clip_sample_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		int32_t libm_variant, int32_t count, const double *time, const int32_t *clip_index, int32_t clip, float *pose_out);
 
 /* Linear blend skinning of a mesh from skin transforms (ABI 10): what mbik_pose_globals' skinned
  * output exists for, on the device and on the stream of the solve.  The semantics are those of

@@ -34,7 +34,7 @@ EXPORTED_SYMBOLS = (
     "mbik_plan_status", "mbik_plan_debug_helper",
     "mbik_solve", "mbik_solve_checked", "mbik_solve_host", "mbik_segment_solve", "mbik_plan_segment_table", "mbik_describe_topology",
     "mbik_group_create", "mbik_group_solve", "mbik_group_destroy", "mbik_multi_create", "mbik_multi_solve",
-    "mbik_multi_skeletons", "mbik_multi_destroy", "mbik_capture_targets", "mbik_pose_globals", "mbik_pose_globals_cpu", "mbik_pose_blend", "mbik_pose_blend_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
+    "mbik_multi_skeletons", "mbik_multi_destroy", "mbik_capture_targets", "mbik_pose_globals", "mbik_pose_globals_cpu", "mbik_pose_blend", "mbik_pose_blend_cpu", "mbik_clipset_create", "mbik_clipset_destroy", "mbik_clip_sample", "mbik_clip_sample_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
     "mbik_skin_vertices", "mbik_skin_vertices_cpu", "mbik_mesh_launch_shape", "mbik_selftest_math",
     "mbik_selftest_libm", "mbik_selftest_div", "mbik_selftest_qcp", "mbik_selftest_point_in_limits", "mbik_selftest_xform", "mbik_selftest_topology", "mbik_plan_create_device", "mbik_last_error",
 )
@@ -77,6 +77,16 @@ class MbikPlanInfo(C.Structure):
 
 class MbikPlanOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("libm_variant", C.c_int32)]
+
+
+class MbikClipTrack(C.Structure):
+    _fields_ = [("bone", C.c_int32), ("channel", C.c_int32), ("interpolation", C.c_int32), ("loop_wrap", C.c_int32),
+                ("key_count", C.c_int32), ("times", C.c_void_p), ("values", C.c_void_p)]
+
+
+class MbikClipDesc(C.Structure):
+    _fields_ = [("length", C.c_double), ("loop_mode", C.c_int32), ("track_count", C.c_int32),
+                ("tracks", C.POINTER(MbikClipTrack))]
 
 
 class MbikError(RuntimeError):
@@ -210,6 +220,14 @@ def load():
     L.mbik_pose_blend.restype = C.c_int32
     L.mbik_pose_blend_cpu.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_float, vp, vp]
     L.mbik_pose_blend_cpu.restype = C.c_int32
+    L.mbik_clipset_create.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MbikClipDesc), C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.mbik_clipset_create.restype = C.c_int32
+    L.mbik_clipset_destroy.argtypes = [vp]
+    L.mbik_clipset_destroy.restype = None
+    L.mbik_clip_sample.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp]
+    L.mbik_clip_sample.restype = C.c_int32
+    L.mbik_clip_sample_cpu.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MbikClipDesc), C.c_int32, C.c_int32, vp, vp, C.c_int32, vp]
+    L.mbik_clip_sample_cpu.restype = C.c_int32
     L.mbik_mesh_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.POINTER(vp)]
     L.mbik_mesh_create.restype = C.c_int32
     L.mbik_mesh_destroy.argtypes = [vp]

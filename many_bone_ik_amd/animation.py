@@ -1,0 +1,186 @@
+"""Animation clip sampling for crowds (include/mbik.h, ABI 12).
+
+`ClipSet` owns one `mbik_clipset`: several clips for one rig, resident on one GPU, bound to a bone
+count and a libm_variant.  `ClipSet.sample()` takes device pointers -- one time (float64) and one
+clip index (int32) per skeleton -- and writes the poses `Plan.solve()` reads; it is asynchronous on
+the given HIP stream.  `clip_sample_cpu()` runs the same code on numpy arrays without a device, and
+`synthetic_clips()` is the seeded clip generator the tests and tools/clip_bench.py use.
+
+A clip is a dict: {"length": seconds, "loop_mode": 0 none | 1 linear, "tracks": [track, ...]}; a
+track is a dict: {"bone", "channel": 0 position | 1 rotation | 2 scale, "interpolation": 0 nearest |
+1 linear, "loop_wrap": 0 | 1, "times": [keys] float64, "values": [keys][3 or 4] float32}.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+
+POSITION, ROTATION, SCALE = 0, 1, 2
+NEAREST, LINEAR = 0, 1
+LOOP_NONE, LOOP_LINEAR = 0, 1
+# floats of a pose record [10] that a channel owns (quaternion xyzw | position | scale)
+CHANNEL_SLICE = {POSITION: slice(4, 7), ROTATION: slice(0, 4), SCALE: slice(7, 10)}
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _descs(clips):
+    """(array of mbik_clip_desc, the objects its pointers refer to)."""
+    keep = []
+    descs = (_lib.MbikClipDesc * max(len(clips), 1))()
+    for d, clip in zip(descs, clips):
+        tracks = clip.get("tracks", [])
+        arr = (_lib.MbikClipTrack * max(len(tracks), 1))()
+        for t, tr in zip(arr, tracks):
+            times = None if tr.get("times") is None else np.ascontiguousarray(tr["times"], np.float64).reshape(-1)
+            values = None if tr.get("values") is None else np.ascontiguousarray(tr["values"], np.float32)
+            n = tr.get("key_count", 0 if times is None else times.shape[0])
+            if values is not None and times is not None and "key_count" not in tr:
+                assert values.size == n * (4 if tr["channel"] == ROTATION else 3), (values.shape, n)
+            keep += [times, values]
+            t.bone, t.channel, t.interpolation = int(tr["bone"]), int(tr["channel"]), int(tr.get("interpolation", LINEAR))
+            t.loop_wrap, t.key_count = int(tr.get("loop_wrap", 1)), int(n)
+            t.times = None if times is None else times.ctypes.data
+            t.values = None if values is None else values.ctypes.data
+        keep.append(arr)
+        d.length, d.loop_mode = float(clip["length"]), int(clip.get("loop_mode", LOOP_NONE))
+        d.track_count = int(clip.get("track_count", len(tracks)))
+        d.tracks = C.cast(arr, C.POINTER(_lib.MbikClipTrack)) if tracks or "track_count" not in clip else None
+    return descs, keep
+
+
+def _rest(bone_count, rest_pose):
+    rest = np.ascontiguousarray(rest_pose, np.float32)
+    assert rest.shape == (bone_count, 10), rest.shape
+    return rest
+
+
+class ClipSet:
+    """Several clips of one rig on one GPU (mbik_clipset_create).  Immutable; close() frees it."""
+
+    def __init__(self, bone_count: int, rest_pose, clips, libm_variant: int = 0, device: int = 0):
+        self._L = _lib.load()
+        rest = _rest(bone_count, rest_pose)
+        descs, keep = _descs(clips)
+        self.bone_count, self.clip_count, self.libm_variant, self.device = int(bone_count), len(clips), libm_variant, device
+        h = C.c_void_p()
+        check(self._L.mbik_clipset_create(self.bone_count, _ptr(rest), len(clips), descs, libm_variant, device, C.byref(h)))
+        del keep
+        self.h = h
+
+    def sample(self, time_ptr: int, pose_out_ptr: int, count: int, clip_index_ptr: int = 0, clip: int = 0, stream: int = 0) -> None:
+        """mbik_clip_sample: pose_out [count][bones][10] from the device arrays time [count] (float64)
+        and clip_index [count] (int32; or the one `clip` for every skeleton); asynchronous on `stream`."""
+        check(self._L.mbik_clip_sample(self.h, count, C.c_void_p(time_ptr or None), C.c_void_p(clip_index_ptr or None), clip,
+                                       C.c_void_p(pose_out_ptr or None), C.c_void_p(stream or None)))
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            self._L.mbik_clipset_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def clip_sample_cpu(bone_count: int, rest_pose, clips, time, clip_index=None, clip: int = 0, libm_variant: int = 0):
+    """mbik_clip_sample_cpu (host only): `time` [count] seconds and `clip_index` [count] (or the one
+    `clip`) -> poses [count][bones][10]."""
+    L = _lib.load()
+    rest = _rest(bone_count, rest_pose)
+    descs, keep = _descs(clips)
+    t = np.ascontiguousarray(time, np.float64).reshape(-1)
+    idx = None if clip_index is None else np.ascontiguousarray(clip_index, np.int32).reshape(-1)
+    assert idx is None or idx.shape == t.shape, (idx.shape, t.shape)
+    out = np.empty((t.shape[0], bone_count, 10), np.float32)
+    check(L.mbik_clip_sample_cpu(bone_count, _ptr(rest), len(clips), descs, libm_variant, t.shape[0], _ptr(t), _ptr(idx), clip,
+                                 _ptr(out)))
+    del keep
+    return out
+
+
+def _unit_quats(rng, n):
+    q = rng.normal(0.0, 1.0, (n, 4))
+    return q / np.linalg.norm(q, axis=1, keepdims=True)
+
+
+def _quat_mul(a, b):
+    x = a[..., 3] * b[..., 0] + a[..., 0] * b[..., 3] + a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1]
+    y = a[..., 3] * b[..., 1] + a[..., 1] * b[..., 3] + a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2]
+    z = a[..., 3] * b[..., 2] + a[..., 2] * b[..., 3] + a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]
+    w = a[..., 3] * b[..., 3] - a[..., 0] * b[..., 0] - a[..., 1] * b[..., 1] - a[..., 2] * b[..., 2]
+    return np.stack([x, y, z, w], axis=-1)
+
+
+def _key_rotations(rng, n):
+    """n unit quaternions, each 10..120 degrees from the one before it and the last at least 10
+    degrees from the first (the pair a wrapping track interpolates)."""
+    q = np.empty((n, 4))
+    q[0] = _unit_quats(rng, 1)[0]
+    k = 1
+    while k < n:
+        ax = rng.normal(0.0, 1.0, 3)
+        ax /= np.linalg.norm(ax)
+        ang = np.radians(rng.uniform(10.0, 120.0))
+        cand = _quat_mul(q[k - 1], np.concatenate([ax * np.sin(ang / 2), [np.cos(ang / 2)]]))
+        if k == n - 1 and 2.0 * np.degrees(np.arccos(min(1.0, abs(float(cand @ q[0]))))) < 10.0:
+            continue
+        q[k] = cand
+        k += 1
+    return q
+
+
+def synthetic_clips(seed: int, bone_count: int, clip_count: int = 3, key_counts=(0, 1, 2, 3, 17), lengths=(1.0, 3.0)):
+    """A seeded clip set for a rig of `bone_count` bones: (rest_pose [bones][10], clips).
+
+    Every (clip, bone, channel) draws its key count from `key_counts` (0: untracked, no track), its
+    interpolation and its loop_wrap at random; clips alternate LOOP_LINEAR and LOOP_NONE, starting
+    with LOOP_LINEAR, with lengths drawn from `lengths`.  A third of the tracks keep their keys
+    strictly inside (0, length), a third have keys exactly at 0 and at length, and a third a key at
+    0 only.  Key rotations are unit quaternions at least 10 degrees apart (the wrap pair included),
+    positions lie in [-1, 1] and scales in [0.5, 1.5]."""
+    rng = np.random.default_rng(seed)
+    B = int(bone_count)
+    rest = np.concatenate([_unit_quats(rng, B), rng.uniform(-1.0, 1.0, (B, 3)), rng.uniform(0.5, 1.5, (B, 3))], axis=1).astype(np.float32)
+    clips = []
+    for c in range(clip_count):
+        length = float(rng.uniform(lengths[0], lengths[1]))
+        tracks = []
+        for bone in range(B):
+            for channel in (POSITION, ROTATION, SCALE):
+                n = int(key_counts[rng.integers(0, len(key_counts))])
+                interpolation, loop_wrap, edge = int(rng.integers(0, 2)), int(rng.integers(0, 2)), int(rng.integers(0, 3))
+                if n == 0:
+                    continue
+                times = np.sort(rng.uniform(0.05 * length, 0.95 * length, n))
+                while n > 1 and np.min(np.diff(times)) <= 0.0:
+                    times = np.sort(rng.uniform(0.05 * length, 0.95 * length, n))
+                if edge >= 1:
+                    times[0] = 0.0
+                if edge == 1 and n > 1:
+                    times[-1] = length
+                if channel == ROTATION:
+                    values = _key_rotations(rng, n)
+                elif channel == POSITION:
+                    values = rng.uniform(-1.0, 1.0, (n, 3))
+                else:
+                    values = rng.uniform(0.5, 1.5, (n, 3))
+                tracks.append(dict(bone=bone, channel=channel, interpolation=interpolation, loop_wrap=loop_wrap,
+                                   times=times.astype(np.float64), values=values.astype(np.float32)))
+        clips.append(dict(length=length, loop_mode=LOOP_LINEAR if c % 2 == 0 else LOOP_NONE, tracks=tracks))
+    return rest, clips

@@ -1,0 +1,213 @@
+// Animation clip sampling, shared by the device kernel (k_clip.hip) and the host entry
+// mbik_clip_sample_cpu (host_clip.cpp): Godot 4.3's Animation::position_track_interpolate,
+// rotation_track_interpolate and scale_track_interpolate (Animation::_interpolate) for
+// INTERPOLATION_NEAREST / INTERPOLATION_LINEAR, LOOP_NONE / LOOP_LINEAR, forward playback and key
+// transitions of 1, for every bone of a skeleton at that skeleton's time in that skeleton's clip.
+// One code path for both sides, made of IEEE-exact operations only (double compares, differences
+// and sums, an integer fmod, gd_math.h's float arithmetic and blend.h's slerp), so the device and
+// the host produce the same bits.  include/mbik.h (ABI 12) states the semantics; DESIGN.md §16.
+#pragma once
+
+#include <cstdint>
+#include <cstring>
+
+#include "blend.h"
+
+namespace mbik {
+
+// ---- the repacked clip set: one blob, on the device for mbik_clipset, on the host for the CPU entry ----
+// One header per (clip, bone, channel), channel 0 position, 1 rotation, 2 scale.  The keys of a
+// channel are key_count consecutive entries of `times` and of `values` from key_off; a value is
+// 4 floats whatever the channel (a position or scale key leaves the fourth 0), so a key is one
+// 16-byte load.  key_count == 0: the channel is untracked (key_off 0).  Both arrays end with one
+// entry that belongs to no track, so index key_off + 0 exists for every header: the per-bone code
+// loads at a clamped index and selects, instead of branching around each load.
+struct ClipHeader {
+	int32_t key_off, key_count, flags, reserved;
+};
+constexpr int kClipLinear = 1; // flags: INTERPOLATION_LINEAR (else nearest)
+constexpr int kClipWrap = 2;   //        loop_mode == LOOP_LINEAR && loop_wrap
+struct ClipInfo {
+	double length;
+	int32_t loop_mode, reserved;
+};
+struct ClipValue {
+	float x, y, z, w;
+};
+struct ClipView {
+	int32_t B, clip_count;
+	const ClipInfo *clips;     // [clip_count]
+	const ClipHeader *headers; // [clip_count][B][3]
+	const double *times;       // [keys + 1]
+	const ClipValue *values;   // [keys + 1]
+	const float *rest;         // [B][10]
+};
+
+GDI uint64_t clip_bits(double x) {
+	union {
+		double d;
+		uint64_t u;
+	} c{x};
+	return c.u;
+}
+GDI bool clip_finite(double x) { return (clip_bits(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
+
+// fmod(x, y) for finite x and finite y > 0: the remainder of the integer significands, shifted one
+// bit at a time, so it is exact -- C's fmod, whose result is always representable -- and made of
+// integer operations and one exact scaling only.  ex - ey iterations: 30 for a time of 1e9 s.
+GDI double clip_fmod(double x, double y) {
+	const double ax = x < 0 ? -x : x;
+	if (ax < y) return x; // (-0 stays -0)
+	uint64_t mx = clip_bits(ax) & 0x000fffffffffffffull, my = clip_bits(y) & 0x000fffffffffffffull;
+	int ex = (int)(clip_bits(ax) >> 52), ey = (int)(clip_bits(y) >> 52);
+	// significands with the leading bit at 52; a subnormal is shifted up, its exponent going below 1
+	if (ex) mx |= 1ull << 52;
+	else
+		for (ex = 1; !(mx >> 52); ex--) mx <<= 1;
+	if (ey) my |= 1ull << 52;
+	else
+		for (ey = 1; !(my >> 52); ey--) my <<= 1;
+	for (int n = ex - ey; n > 0; n--) {
+		if (mx >= my) mx -= my;
+		mx <<= 1;
+	}
+	if (mx >= my) mx -= my;
+	const double r = ldexp((double)(int64_t)mx, ey - 1075); // mx < 2^53 and r < y is a multiple of x's and y's last bits: exact
+	return x < 0 ? -r : r;
+}
+
+// Step 3: the time a clip is sampled at.  LOOP_NONE clamps to [0, length]; LOOP_LINEAR is
+// Math::fposmod.  t is finite.
+GDI double clip_time(double t, double length, int loop_mode) {
+	if (loop_mode == 0) return t < 0 ? 0.0 : (t > length ? length : t);
+	double v = clip_fmod(t, length);
+	if (v < 0) v += length;
+	v += 0.0;
+	return v;
+}
+
+// One channel of one bone: its keys (T = times + key_off, V likewise), and `pos`, the number of
+// keys the search knows to be <= the time.
+struct ClipChan {
+	const double *T;
+	const ClipValue *V;
+	int n, flags, pos;
+};
+GDI ClipChan clip_chan(const ClipView &v, const ClipHeader &h) { return ClipChan{v.times + h.key_off, v.values + h.key_off, h.key_count, h.flags, 0}; }
+
+// One step of the three channels' searches for their last key <= tp: pos grows by `step` when the
+// key that would then be the last one is <= tp.  Over step = 2^k ... 1 with 2^k the highest power
+// of two <= n (a larger first step changes nothing), pos ends as the count of keys <= tp.  The
+// three loads are issued before any of them is used, at an index clamped into the channel's keys
+// (0 for a channel without keys: the arrays' spare entry at worst), so a lane has three
+// independent loads in flight per step, not three round trips one after the other.
+GDI void clip_search_step(ClipChan &a, ClipChan &b, ClipChan &c, int step, double tp) {
+	const int ka = a.pos + step - 1, kb = b.pos + step - 1, kc = c.pos + step - 1;
+	const bool ia = ka < a.n, ib = kb < b.n, ic = kc < c.n;
+	const double ta = a.T[ia ? ka : 0], tb = b.T[ib ? kb : 0], tc = c.T[ic ? kc : 0];
+	a.pos += ia && ta <= tp ? step : 0;
+	b.pos += ib && tb <= tp ? step : 0;
+	c.pos += ic && tc <= tp ? step : 0;
+}
+
+// Step 5 up to the loads: the keys a and b a channel's value comes from, and how.  i = pos - 1 is
+// the last key <= tp, or -1.  A channel without keys picks index 0 as a copy (its value is not used).
+enum ClipMode : int {
+	kClipCopy = 0,       // V[a]
+	kClipInterior = 1,   // delta = T[b] - T[a], from = tp - T[a]
+	kClipWrapAfter = 2,  // a = n-1, b = 0: delta = (length - T[a]) + T[b], from = tp - T[a]
+	kClipWrapBefore = 3, //                 the same delta,                 from = (length - T[a]) + tp
+};
+struct ClipPick {
+	int a, b, mode;
+};
+GDI ClipPick clip_pick(const ClipChan &ch) {
+	const int n = ch.n, i = ch.pos - 1;
+	const bool wrap = (ch.flags & kClipWrap) != 0;
+	if (n <= 1) return ClipPick{0, 0, kClipCopy};
+	if (!wrap && i < 0) return ClipPick{0, 0, kClipCopy};
+	if (!wrap && i == n - 1) return ClipPick{n - 1, n - 1, kClipCopy};
+	const bool linear = (ch.flags & kClipLinear) != 0;
+	if (i >= 0 && i < n - 1) return ClipPick{i, i + 1, linear ? kClipInterior : kClipCopy};
+	return ClipPick{n - 1, 0, linear ? (i < 0 ? kClipWrapBefore : kClipWrapAfter) : kClipCopy};
+}
+// The weight c between the two keys of a pick that is not a copy.  Every difference and sum in
+// double, rounded once to float; the quotient is IEEE float division.
+GDI float clip_weight(int mode, double Ta, double Tb, double tp, double length) {
+	float delta, from;
+	if (mode == kClipInterior) {
+		delta = (float)(Tb - Ta);
+		from = (float)(tp - Ta);
+	} else {
+		const double end = length - Ta;
+		delta = (float)(end + Tb);
+		from = mode == kClipWrapBefore ? (float)(end + tp) : (float)(tp - Ta);
+	}
+	return fabsf(delta) < (float)CMP_EPSILON ? 0.0f : gd_div(from, delta);
+}
+
+GDI float clip_nan() {
+	union {
+		uint32_t u;
+		float f;
+	} c{0x7fc00000u};
+	return c.f;
+}
+
+// A position or scale channel into out[0..2] from its loaded keys.  rest: the rest pose's three floats.
+GDI void clip_store_vec(const ClipChan &ch, const ClipPick &p, float c, const ClipValue &a, const ClipValue &b, const float *rest,
+		float *out) {
+	if (ch.n == 0) {
+		out[0] = rest[0], out[1] = rest[1], out[2] = rest[2];
+	} else if (p.mode == kClipCopy) {
+		out[0] = a.x, out[1] = a.y, out[2] = a.z;
+	} else {
+		const V3 r = v3(a.x, a.y, a.z) + (v3(b.x, b.y, b.z) - v3(a.x, a.y, a.z)) * c; // Vector3::lerp
+		out[0] = blend_canon(r.x), out[1] = blend_canon(r.y), out[2] = blend_canon(r.z);
+	}
+}
+
+// One bone of one skeleton: out10 = the pose (quaternion xyzw, position, scale) of `bone` at raw
+// time t in clip `clip`.  What a lane waits for is memory, so the loads are arranged in as few
+// dependent rounds as the data allows: the clip's length and the three headers; the search steps,
+// three loads each; then the two key times and the two key values of all three channels at once.
+GDI void clip_sample_bone(const ClipView &v, int clip, int bone, double t, int lv, float *out10) {
+	if (clip < 0 || clip >= v.clip_count) {
+		for (int f = 0; f < 10; f++) out10[f] = clip_nan();
+		return;
+	}
+	const ClipInfo info = v.clips[clip];
+	const ClipHeader *h = v.headers + ((int64_t)clip * v.B + bone) * 3;
+	ClipChan pos = clip_chan(v, h[0]), rot = clip_chan(v, h[1]), scl = clip_chan(v, h[2]);
+	const float *rest = v.rest + (int64_t)bone * 10;
+	if (!clip_finite(t)) { // no key is read
+		for (int f = 0; f < 4; f++) out10[f] = rot.n ? clip_nan() : rest[f];
+		for (int f = 4; f < 7; f++) out10[f] = pos.n ? clip_nan() : rest[f];
+		for (int f = 7; f < 10; f++) out10[f] = scl.n ? clip_nan() : rest[f];
+		return;
+	}
+	const double tp = clip_time(t, info.length, info.loop_mode);
+	const int nrs = rot.n > scl.n ? rot.n : scl.n, nmax = pos.n > nrs ? pos.n : nrs;
+	int step = 1;
+	while (step <= (nmax >> 1)) step <<= 1; // the highest power of two <= nmax
+	for (; step > 0; step >>= 1) clip_search_step(pos, rot, scl, step, tp);
+	const ClipPick pp = clip_pick(pos), pr = clip_pick(rot), ps = clip_pick(scl);
+	// twelve independent loads
+	const double pTa = pos.T[pp.a], pTb = pos.T[pp.b], rTa = rot.T[pr.a], rTb = rot.T[pr.b], sTa = scl.T[ps.a], sTb = scl.T[ps.b];
+	const ClipValue pVa = pos.V[pp.a], pVb = pos.V[pp.b], rVa = rot.V[pr.a], rVb = rot.V[pr.b], sVa = scl.V[ps.a], sVb = scl.V[ps.b];
+	const float pc = clip_weight(pp.mode, pTa, pTb, tp, info.length), rc = clip_weight(pr.mode, rTa, rTb, tp, info.length),
+				sc = clip_weight(ps.mode, sTa, sTb, tp, info.length);
+	if (rot.n == 0) {
+		out10[0] = rest[0], out10[1] = rest[1], out10[2] = rest[2], out10[3] = rest[3];
+	} else if (pr.mode == kClipCopy) {
+		out10[0] = rVa.x, out10[1] = rVa.y, out10[2] = rVa.z, out10[3] = rVa.w;
+	} else {
+		// Quaternion::slerp, not renormalised; a wave none of whose lanes gets here skips it
+		const Q r = blend_slerp(q4(rVa.x, rVa.y, rVa.z, rVa.w), q4(rVb.x, rVb.y, rVb.z, rVb.w), rc, lv);
+		out10[0] = blend_canon(r.x), out10[1] = blend_canon(r.y), out10[2] = blend_canon(r.z), out10[3] = blend_canon(r.w);
+	}
+	clip_store_vec(pos, pp, pc, pVa, pVb, rest + 4, out10 + 4);
+	clip_store_vec(scl, ps, sc, sVa, sVb, rest + 7, out10 + 7);
+}
+
+} // namespace mbik

@@ -1,0 +1,179 @@
+// Animation clip sampling (include/mbik.h, ABI 12): the clip-set handle, mbik_clip_sample, which
+// launches k_clip.hip's kernel on the set's device, and mbik_clip_sample_cpu, which runs the same
+// per-bone code (clip.h) on the host.  The front stage of a frame: the poses mbik_solve reads are
+// sampled on the solve's stream from a time and a clip index per skeleton.  DESIGN.md §16.
+#include "host.h"
+
+#include <cmath>
+
+#include "clip.h"
+
+using namespace mbik_host;
+
+struct mbik_clipset {
+	int device = 0;
+	int32_t B = 0, clip_count = 0, libm = 0;
+	unsigned char *d_blob = nullptr;
+	mbik::ClipView view{}; // device pointers into d_blob
+};
+
+namespace {
+
+// The repacked tables (clip.h), checked: everything the per-bone code indexes without a test.
+struct Packed {
+	std::vector<mbik::ClipInfo> clips;
+	std::vector<mbik::ClipHeader> headers;
+	std::vector<double> times;
+	std::vector<mbik::ClipValue> values;
+	std::vector<float> rest;
+	mbik::ClipView view(int32_t B) const {
+		return mbik::ClipView{B, (int32_t)clips.size(), clips.data(), headers.data(), times.data(), values.data(), rest.data()};
+	}
+};
+
+int pack(int32_t B, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips, int32_t libm_variant, Packed &out) {
+	if (B < 0 || clip_count < 0) return fail(MBIK_EINVAL, "negative count");
+	if (!rest_pose) return fail(MBIK_EINVAL, "null rest_pose");
+	if (clip_count == 0) return fail(MBIK_EINVAL, "a clip set needs at least one clip");
+	if (!clips) return fail(MBIK_EINVAL, "null clips");
+	if (libm_variant != MBIK_LIBM_VARIANT_FMA && libm_variant != MBIK_LIBM_VARIANT_SSE2) return fail(MBIK_EINVAL, "unknown libm_variant");
+	if ((int64_t)clip_count * B * 3 > INT32_MAX) return fail(MBIK_EUNSUPPORTED, "more than 2^31 (clip, bone, channel) headers");
+	out.clips.resize(clip_count);
+	out.headers.assign((size_t)clip_count * B * 3, mbik::ClipHeader{0, 0, 0, 0});
+	out.rest.assign(rest_pose, rest_pose + (size_t)B * 10);
+	for (int32_t c = 0; c < clip_count; c++) {
+		const mbik_clip_desc &d = clips[c];
+		const std::string where = "clip " + std::to_string(c);
+		if (!(d.length > 0) || !std::isfinite(d.length)) return fail(MBIK_EINVAL, where + ": length must be positive and finite");
+		if (d.loop_mode != 0 && d.loop_mode != 1) return fail(MBIK_EINVAL, where + ": unknown loop_mode " + std::to_string(d.loop_mode));
+		if (d.track_count < 0) return fail(MBIK_EINVAL, where + ": negative track_count");
+		if (d.track_count > 0 && !d.tracks) return fail(MBIK_EINVAL, where + ": null tracks");
+		out.clips[c] = mbik::ClipInfo{d.length, d.loop_mode, 0};
+		for (int32_t k = 0; k < d.track_count; k++) {
+			const mbik_clip_track &t = d.tracks[k];
+			const std::string tw = where + " track " + std::to_string(k);
+			if (t.bone < 0 || t.bone >= B) return fail(MBIK_EINVAL, tw + ": bone " + std::to_string(t.bone) + " outside [0, " + std::to_string(B) + ")");
+			if (t.channel < 0 || t.channel > 2) return fail(MBIK_EINVAL, tw + ": unknown channel " + std::to_string(t.channel));
+			if (t.interpolation != 0 && t.interpolation != 1) return fail(MBIK_EINVAL, tw + ": unknown interpolation " + std::to_string(t.interpolation));
+			if (t.key_count < 0) return fail(MBIK_EINVAL, tw + ": negative key_count");
+			if (t.key_count == 0) continue; // the same as no track
+			if (!t.times || !t.values) return fail(MBIK_EINVAL, tw + ": null times or values");
+			mbik::ClipHeader &h = out.headers[((size_t)c * B + t.bone) * 3 + t.channel];
+			if (h.key_count) return fail(MBIK_EINVAL, tw + ": a second track with keys for bone " + std::to_string(t.bone) + " channel " + std::to_string(t.channel));
+			if (out.times.size() + (size_t)t.key_count > (size_t)INT32_MAX) return fail(MBIK_EUNSUPPORTED, "more than 2^31 keys in a clip set");
+			for (int32_t i = 0; i < t.key_count; i++) {
+				const double x = t.times[i];
+				if (!std::isfinite(x) || !(x >= 0) || !(x <= d.length))
+					return fail(MBIK_EINVAL, tw + ": key " + std::to_string(i) + " has a time that is not finite or outside [0, length]");
+				if (i > 0 && !(x > t.times[i - 1])) return fail(MBIK_EINVAL, tw + ": key times are not strictly increasing at key " + std::to_string(i));
+			}
+			h.key_off = (int32_t)out.times.size(), h.key_count = t.key_count;
+			h.flags = (t.interpolation == 1 ? mbik::kClipLinear : 0) | (d.loop_mode == 1 && t.loop_wrap ? mbik::kClipWrap : 0);
+			const int w = t.channel == 1 ? 4 : 3;
+			for (int32_t i = 0; i < t.key_count; i++) {
+				const float *v = t.values + (size_t)i * w;
+				out.times.push_back(t.times[i]);
+				out.values.push_back(mbik::ClipValue{v[0], v[1], v[2], w == 4 ? v[3] : 0.0f});
+			}
+		}
+	}
+	// the spare entry that makes index key_off + 0 valid for every header (clip.h)
+	out.times.push_back(0.0);
+	out.values.push_back(mbik::ClipValue{0.0f, 0.0f, 0.0f, 0.0f});
+	return MBIK_OK;
+}
+
+// The checks of a sampling call past the set's own; 0 = go on, 1 = nothing to do.
+int check_call(int32_t B, int32_t clip_count, int32_t count, const double *time, const int32_t *clip_index, int32_t clip,
+		const float *pose_out) {
+	if (count < 0) return fail(MBIK_EINVAL, "negative count");
+	if (count == 0 || B == 0) return 1;
+	if (!time) return fail(MBIK_EINVAL, "null time");
+	if (!pose_out) return fail(MBIK_EINVAL, "null pose_out");
+	if (!clip_index && (clip < 0 || clip >= clip_count))
+		return fail(MBIK_EINVAL, "clip " + std::to_string(clip) + " outside the set's " + std::to_string(clip_count) + " clips");
+	return 0;
+}
+
+size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+} // namespace
+
+extern "C" {
+
+int32_t mbik_clipset_create(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		int32_t libm_variant, int32_t device, mbik_clipset **out) {
+	if (!out) return fail(MBIK_EINVAL, "null out");
+	*out = nullptr;
+	Packed pk;
+	if (int rc = pack(bone_count, rest_pose, clip_count, clips, libm_variant, pk)) return rc;
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MBIK_ENODEV, "no HIP device visible");
+	if (device < 0 || device >= ndev) return fail(MBIK_EINVAL, "device index out of range");
+	std::unique_ptr<mbik_clipset> s(new mbik_clipset());
+	s->device = device, s->B = bone_count, s->clip_count = clip_count, s->libm = libm_variant;
+	// one blob: clip infos, headers, times, values, rest pose, each from a 16-byte boundary
+	const size_t n_info = pk.clips.size() * sizeof(mbik::ClipInfo), n_head = pk.headers.size() * sizeof(mbik::ClipHeader),
+				 n_time = pk.times.size() * sizeof(double), n_val = pk.values.size() * sizeof(mbik::ClipValue),
+				 n_rest = pk.rest.size() * sizeof(float);
+	const size_t o_info = 0, o_head = up16(o_info + n_info), o_time = up16(o_head + n_head), o_val = up16(o_time + n_time),
+				 o_rest = up16(o_val + n_val), bytes = up16(o_rest + n_rest) + 16;
+	std::vector<unsigned char> blob(bytes, 0);
+	std::memcpy(blob.data() + o_info, pk.clips.data(), n_info);
+	if (n_head) std::memcpy(blob.data() + o_head, pk.headers.data(), n_head);
+	if (n_time) std::memcpy(blob.data() + o_time, pk.times.data(), n_time);
+	if (n_val) std::memcpy(blob.data() + o_val, pk.values.data(), n_val);
+	if (n_rest) std::memcpy(blob.data() + o_rest, pk.rest.data(), n_rest);
+	DeviceGuard guard(device);
+	void *d = nullptr;
+	if (hipMalloc(&d, bytes) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc failed for the clip set");
+	if (hipMemcpy(d, blob.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+		(void)hipFree(d);
+		return fail(MBIK_EHIP, "hipMemcpy failed for the clip set");
+	}
+	unsigned char *b = static_cast<unsigned char *>(d);
+	s->d_blob = b;
+	s->view = mbik::ClipView{bone_count, clip_count, reinterpret_cast<const mbik::ClipInfo *>(b + o_info),
+			reinterpret_cast<const mbik::ClipHeader *>(b + o_head), reinterpret_cast<const double *>(b + o_time),
+			reinterpret_cast<const mbik::ClipValue *>(b + o_val), reinterpret_cast<const float *>(b + o_rest)};
+	*out = s.release();
+	return MBIK_OK;
+}
+
+void mbik_clipset_destroy(mbik_clipset *s) {
+	if (!s) return;
+	if (s->d_blob) {
+		DeviceGuard guard(s->device);
+		(void)hipFree(s->d_blob);
+	}
+	delete s;
+}
+
+int32_t mbik_clip_sample(mbik_clipset *s, int32_t count, const double *time, const int32_t *clip_index, int32_t clip, float *pose_out,
+		void *hip_stream) {
+	if (!s) return fail(MBIK_EINVAL, "null clip set");
+	const int rc = check_call(s->B, s->clip_count, count, time, clip_index, clip, pose_out);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	if ((int64_t)count * s->B > (int64_t)INT32_MAX * 256) return fail(MBIK_EUNSUPPORTED, "more than 2^39 bones in one call");
+	DeviceGuard guard(s->device);
+	hipError_t e = mbik::launch_clip(reinterpret_cast<hipStream_t>(hip_stream), s->view, s->libm, (int64_t)count * s->B, time, clip_index,
+			clip, pose_out);
+	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("clip sample launch failed: ") + hipGetErrorString(e));
+	return MBIK_OK;
+}
+
+int32_t mbik_clip_sample_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		int32_t libm_variant, int32_t count, const double *time, const int32_t *clip_index, int32_t clip, float *pose_out) {
+	Packed pk;
+	if (int rc = pack(bone_count, rest_pose, clip_count, clips, libm_variant, pk)) return rc;
+	const int rc = check_call(bone_count, clip_count, count, time, clip_index, clip, pose_out);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	const mbik::ClipView v = pk.view(bone_count);
+	for (int64_t s = 0; s < count; s++) {
+		const int32_t c = clip_index ? clip_index[s] : clip;
+		for (int32_t b = 0; b < bone_count; b++) mbik::clip_sample_bone(v, c, b, time[s], libm_variant, pose_out + (s * bone_count + b) * 10);
+	}
+	return MBIK_OK;
+}
+
+} // extern "C"

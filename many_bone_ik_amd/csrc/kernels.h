@@ -176,6 +176,11 @@ hipError_t launch_skin(hipStream_t st, int K, int count, int B, int V, int S, in
 // of static LDS; influence_per_skeleton (device, [count]) overrides influence when given; pose_out may be pose_in or pose_mod.
 hipError_t launch_blend(hipStream_t st, int64_t total_bones, int B, int libm, float influence, const float *influence_per_skeleton,
 		const float *pose_in, const float *pose_mod, float *pose_out);
+// k_clip.hip: mbik_clip_sample (clip.h).  One thread per bone of the total_bones = count * v.B, 256 bones a block, 10 KiB of
+// static LDS; v's tables are device memory; clip_index (device, [count]) overrides clip when given.
+struct ClipView;
+hipError_t launch_clip(hipStream_t st, const ClipView &v, int libm, int64_t total_bones, const double *time, const int32_t *clip_index,
+		int clip, float *pose_out);
 #ifdef MBIK_PROF
 // Diagnostic cycle accounting (-DMBIK_PROF): each kernel TU has its own counters; adds them to
 // out[24] and clears them.
