@@ -57,7 +57,7 @@ extern "C" {
 #define MBIK_EUNSUPPORTED (-4)
 #define MBIK_ENODEV (-5)
 
-#define MBIK_ABI_VERSION 12
+#define MBIK_ABI_VERSION 13
 
 typedef struct mbik_plan mbik_plan;
 typedef struct mbik_group mbik_group;
@@ -330,7 +330,9 @@ int32_t mbik_plan_autotune(mbik_plan *plan, int32_t first, int32_t count, const 
  *     the same limit: a rig may have at most MBIK_FK_MAX_BONES bones there (the solve itself
  *     takes larger rigs);
  *   - mbik_skin_vertices keeps one skeleton's skin transforms (12 floats per bone) in LDS with the
- *     same limit: a mesh may be bound to at most MBIK_SKIN_MAX_BONES bones (mbik_mesh_create). */
+ *     same limit: a mesh may be bound to at most MBIK_SKIN_MAX_BONES bones (mbik_mesh_create);
+ *   - mbik_skin_vertices_shaped stages a skeleton's shape weights with its skin transforms:
+ *     bone_count * 48 + shape_count * 4 bytes must fit the same limit (mbik_mesh_create_shaped). */
 #define MBIK_MAX_PATH_BONES 4096
 #define MBIK_MAX_LDS_BYTES (160 * 1024)
 #define MBIK_FK_MAX_BONES 1861
@@ -551,6 +553,68 @@ int32_t mbik_skin_vertices_cpu(int32_t bone_count, int32_t vertex_count, int32_t
  * pieces of the vertex range; the grid is skeleton tiles x vertex chunks, so that a small count
  * with a large mesh still fills the device.  Either output may be NULL. */
 int32_t mbik_mesh_launch_shape(const mbik_mesh *mesh, int32_t count, int32_t *skeletons_per_block, int32_t *vertex_chunks);
+
+/* Blend shapes (morph targets) in front of the skinning (ABI 13): the first half of Godot 4.3's
+ * skeleton compute shader, BLEND_SHAPE_MODE_RELATIVE and BLEND_SHAPE_MODE_NORMALIZED, so that the
+ * skeletons of one batch need not be the same body.  A shaped mesh carries P >= 1 shapes --
+ *   shapes.positions [shape_count][vertex_count][3]
+ *   shapes.normals   [shape_count][vertex_count][3], given exactly when the mesh has normals
+ * -- shared by every skeleton, and each skeleton brings P weights.  For vertex v of skeleton s with
+ * c_j = shape_weights[s][j], float32, unfused, in this order:
+ *   bp = (0,0,0); bn = (0,0,0); total = 0.0f
+ *   for j = 0 .. P-1 ascending, if fabsf(c_j) > 0.0001f (the shader's test; false for NaN, so a
+ *   NaN weight is skipped):
+ *       bp = bp + shapes.positions[j][v] * c_j       (V3 * float, then V3 + V3)
+ *       bn = bn + shapes.normals[j][v] * c_j         (meshes with normals only)
+ *       total = total + c_j
+ *   pos = positions[v]; nrm = normals[v]
+ *   mode normalized: base_w = 1.0f - total; pos = pos * base_w; nrm = nrm * base_w
+ *   pos = pos + bp
+ *   nrm = normalized(nrm + bn)   x / sqrt((x*x + y*y) + z*z) per component with IEEE sqrt and
+ *                                division; the zero vector stays zero
+ * and mbik_skin_vertices' blend and transform then run on pos and nrm, unchanged.  It follows that
+ * with every weight skipped a relative-mode position is positions[v] + (+0,+0,+0) (the base's bits,
+ * except that -0 becomes +0), that the normal of a shaped call is always renormalised before the
+ * bone transform (the shader's behaviour; mbik_skin_vertices never renormalises), and that
+ * infinite weights and non-finite shape data propagate.  mbik_skin_vertices_shaped_cpu is the
+ * specification and the device gives the same bits.  Deviations from Godot: the shader reads
+ * octahedral-packed normals and compressed vertex formats, here every array is float32; tangents
+ * are not covered.
+ *
+ * mbik_mesh_create_shaped is mbik_mesh_create with shapes: the same arguments and checks, plus
+ * MBIK_EINVAL for a null `shapes`, a struct_size below sizeof(mbik_mesh_shapes), shape_count < 1,
+ * an unknown mode, null shapes.positions on a mesh with vertices, and normals on exactly one of
+ * the mesh and the shapes; MBIK_EUNSUPPORTED when bone_count * 48 + shape_count * 4 exceeds
+ * MBIK_MAX_LDS_BYTES (one skeleton's matrices and shape weights are staged together).  The shape
+ * arrays are copied like the mesh's.  mbik_skin_vertices on a shaped mesh skins the base arrays
+ * with that call's semantics and bits, without shapes and without renormalisation;
+ * mbik_mesh_launch_shape on a shaped mesh reports what mbik_skin_vertices_shaped would use (the
+ * LDS of one skeleton is bone_count * 48 + shape_count * 4 bytes there). */
+#define MBIK_SHAPE_MODE_RELATIVE 0
+#define MBIK_SHAPE_MODE_NORMALIZED 1
+typedef struct mbik_mesh_shapes {
+	int32_t struct_size;       /* sizeof(mbik_mesh_shapes) */
+	int32_t shape_count;       /* P >= 1 */
+	int32_t mode;              /* MBIK_SHAPE_MODE_* */
+	const float *positions;    /* [shape_count][vertex_count][3] */
+	const float *normals;      /* [shape_count][vertex_count][3], or NULL for a mesh without normals */
+} mbik_mesh_shapes;
+int32_t mbik_mesh_create_shaped(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
+		const float *normals, const int32_t *bone_indices, const float *weights, const mbik_mesh_shapes *shapes,
+		int32_t device, mbik_mesh **out_mesh);
+/* mbik_skin_vertices with blend shapes: shape_weights is [count][shape_count] in device memory, read
+ * by the kernel, never by the host; the other arguments as for mbik_skin_vertices.  MBIK_EINVAL:
+ * a mesh without shapes, null shape_weights with count > 0 and vertices, shape_weights overlapping
+ * an output, and everything mbik_skin_vertices refuses.  count == 0 or a mesh without vertices
+ * returns MBIK_OK without a launch.  Buffers need float alignment only. */
+int32_t mbik_skin_vertices_shaped(mbik_mesh *mesh, int32_t count, const float *skin, const float *shape_weights,
+		float *out_positions, float *out_normals, void *hip_stream);
+/* Host-only (no device needed): the same arithmetic from the same code on host buffers, with
+ * mbik_mesh_create_shaped's and mbik_skin_vertices_shaped's checks except the LDS limit (any bone
+ * and shape count). */
+int32_t mbik_skin_vertices_shaped_cpu(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
+		const float *normals, const int32_t *bone_indices, const float *weights, const mbik_mesh_shapes *shapes, int32_t count,
+		const float *skin, const float *shape_weights, float *out_positions, float *out_normals);
 
 /* Heterogeneous batches: several plans (distinct rigs, e.g. a crowd of different characters)
  * solved by ONE launch, each plan with its own layout.  The reference runs one

@@ -35,7 +35,8 @@ EXPORTED_SYMBOLS = (
     "mbik_solve", "mbik_solve_checked", "mbik_solve_host", "mbik_segment_solve", "mbik_plan_segment_table", "mbik_describe_topology",
     "mbik_group_create", "mbik_group_solve", "mbik_group_destroy", "mbik_multi_create", "mbik_multi_solve",
     "mbik_multi_skeletons", "mbik_multi_destroy", "mbik_capture_targets", "mbik_pose_globals", "mbik_pose_globals_cpu", "mbik_pose_blend", "mbik_pose_blend_cpu", "mbik_clipset_create", "mbik_clipset_destroy", "mbik_clip_sample", "mbik_clip_sample_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
-    "mbik_skin_vertices", "mbik_skin_vertices_cpu", "mbik_mesh_launch_shape", "mbik_selftest_math",
+    "mbik_skin_vertices", "mbik_skin_vertices_cpu", "mbik_mesh_launch_shape", "mbik_mesh_create_shaped", "mbik_skin_vertices_shaped",
+    "mbik_skin_vertices_shaped_cpu", "mbik_selftest_math",
     "mbik_selftest_libm", "mbik_selftest_div", "mbik_selftest_qcp", "mbik_selftest_point_in_limits", "mbik_selftest_xform", "mbik_selftest_topology", "mbik_plan_create_device", "mbik_last_error",
 )
 
@@ -87,6 +88,14 @@ class MbikClipTrack(C.Structure):
 class MbikClipDesc(C.Structure):
     _fields_ = [("length", C.c_double), ("loop_mode", C.c_int32), ("track_count", C.c_int32),
                 ("tracks", C.POINTER(MbikClipTrack))]
+
+
+class MbikMeshShapes(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("shape_count", C.c_int32), ("mode", C.c_int32), ("positions", C.c_void_p),
+                ("normals", C.c_void_p)]
+
+
+SHAPE_MODES = {"relative": 0, "normalized": 1}  # MBIK_SHAPE_MODE_*
 
 
 class MbikError(RuntimeError):
@@ -238,6 +247,14 @@ def load():
     L.mbik_skin_vertices_cpu.restype = C.c_int32
     L.mbik_mesh_launch_shape.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.mbik_mesh_launch_shape.restype = C.c_int32
+    L.mbik_mesh_create_shaped.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.POINTER(MbikMeshShapes), C.c_int32,
+                                          C.POINTER(vp)]
+    L.mbik_mesh_create_shaped.restype = C.c_int32
+    L.mbik_skin_vertices_shaped.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
+    L.mbik_skin_vertices_shaped.restype = C.c_int32
+    L.mbik_skin_vertices_shaped_cpu.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.POINTER(MbikMeshShapes), C.c_int32,
+                                                vp, vp, vp, vp]
+    L.mbik_skin_vertices_shaped_cpu.restype = C.c_int32
     L.mbik_last_error.argtypes = []
     L.mbik_last_error.restype = C.c_char_p
     _lib = L

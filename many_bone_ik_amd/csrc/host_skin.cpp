@@ -2,9 +2,11 @@
 // mbik_skin_vertices, which launches k_skin.hip's kernel on the mesh's device, and
 // mbik_skin_vertices_cpu, which runs the same per-vertex code (skin.h) on the host.  The
 // semantics are those of Godot's skeleton compute shader on ArrayMesh surface arrays;
-// DESIGN.md §14.
+// DESIGN.md §14.  Blend shapes in front of the skinning (ABI 13, morph.h):
+// mbik_mesh_create_shaped, mbik_skin_vertices_shaped and mbik_skin_vertices_shaped_cpu.
 #include "host.h"
 
+#include "morph.h"
 #include "skin.h"
 
 using namespace mbik_host;
@@ -13,7 +15,8 @@ struct mbik_mesh {
 	int device = 0, cu_count = 256;
 	int32_t B = 0, V = 0, K = 4;
 	bool normals = false;
-	unsigned char *d_mesh = nullptr; // skin_layout()'s planes
+	int32_t P = 0, mode = 0;         // shapes (P == 0: a mesh without)
+	unsigned char *d_mesh = nullptr; // skin_layout()'s planes, then morph_layout()'s
 };
 
 namespace {
@@ -42,8 +45,9 @@ struct SkinShape {
 // S: as many skeletons as the LDS target holds.  Vertex chunks: enough for kSkinBlocksPerCu blocks
 // a CU, but no chunk shorter than 256 vertices or than 8 vertices per bone -- every block stages
 // its S x B matrices again, 12 LDS dword writes a bone against 3 K quad reads a vertex.
-SkinShape shape_of(const mbik_mesh *m, int64_t count) {
-	const int64_t per = std::max<int64_t>(48, (int64_t)m->B * 48);
+// shaped: a block also stages its skeletons' shape weights (mbik_skin_vertices_shaped).
+SkinShape shape_of(const mbik_mesh *m, int64_t count, bool shaped) {
+	const int64_t per = std::max<int64_t>(48, (int64_t)m->B * 48) + (shaped ? (int64_t)m->P * 4 : 0);
 	SkinShape sh;
 	sh.S = (int)std::max<int64_t>(1, std::min<int64_t>({kSkinBlockLdsTarget / per, kSkinMaxSkeletonsPerBlock, count}));
 	const int64_t tiles = std::max<int64_t>(1, (count + sh.S - 1) / sh.S);
@@ -83,12 +87,32 @@ int check_call(int32_t B, int32_t V, bool mesh_normals, int32_t count, const flo
 	return 0;
 }
 
-} // namespace
+// The shape checks mbik_mesh_create_shaped and mbik_skin_vertices_shaped_cpu share; lds_limit as morph_check's.
+int check_shapes(int32_t B, int32_t V, bool mesh_normals, const mbik_mesh_shapes *sh, int64_t lds_limit) {
+	if (!sh) return fail(MBIK_EINVAL, "null shapes");
+	if (sh->struct_size < (int32_t)sizeof(mbik_mesh_shapes)) return fail(MBIK_EINVAL, "mbik_mesh_shapes.struct_size is too small");
+	const mbik::MorphCheck c = mbik::morph_check(B, V, mesh_normals, sh->shape_count, sh->mode, sh->positions, sh->normals, lds_limit);
+	if (c == mbik::MORPH_TOO_LARGE)
+		return fail(MBIK_EUNSUPPORTED, "rig has " + std::to_string(B) + " bones and " + std::to_string(sh->shape_count) +
+				" shapes: " + mbik::morph_check_text(c) + " (MBIK_MAX_LDS_BYTES)");
+	if (c != mbik::MORPH_OK) return fail(MBIK_EINVAL, mbik::morph_check_text(c));
+	return MBIK_OK;
+}
 
-extern "C" {
+// The checks of a shaped call's weights, past check_call's.
+int check_shape_weights(int32_t V, int32_t P, int32_t count, const float *shape_weights, const float *out_positions,
+		const float *out_normals) {
+	if (!shape_weights) return fail(MBIK_EINVAL, "null shape_weights");
+	const size_t nw = (size_t)count * P * sizeof(float), nout = (size_t)count * V * 3 * sizeof(float);
+	if (overlap(shape_weights, nw, out_positions, nout)) return fail(MBIK_EINVAL, "out_positions overlaps shape_weights");
+	if (out_normals && overlap(shape_weights, nw, out_normals, nout)) return fail(MBIK_EINVAL, "out_normals overlaps shape_weights");
+	return MBIK_OK;
+}
 
-int32_t mbik_mesh_create(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions, const float *normals,
-		const int32_t *bone_indices, const float *weights, int32_t device, mbik_mesh **out_mesh) {
+// mbik_mesh_create (shaped == false: `shapes` is not looked at) and mbik_mesh_create_shaped
+int create_mesh(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions, const float *normals,
+		const int32_t *bone_indices, const float *weights, bool shaped, const mbik_mesh_shapes *shapes, int32_t device,
+		mbik_mesh **out_mesh) {
 	if (!out_mesh) return fail(MBIK_EINVAL, "null out_mesh");
 	*out_mesh = nullptr;
 	if (influences != 4 && influences != 8) return fail(MBIK_EINVAL, mbik::skin_check_text(mbik::SKIN_BAD_INFLUENCES));
@@ -97,19 +121,24 @@ int32_t mbik_mesh_create(int32_t bone_count, int32_t vertex_count, int32_t influ
 	if (bone_count > mbik::kSkinMaxBones)
 		return fail(MBIK_EUNSUPPORTED, "rig has " + std::to_string(bone_count) + " bones; a mesh supports at most " +
 				std::to_string(mbik::kSkinMaxBones) + " (MBIK_SKIN_MAX_BONES: one skeleton's matrices must fit 160 KiB of LDS)");
+	if (shaped)
+		if (int rc = check_shapes(bone_count, vertex_count, normals != nullptr, shapes, mbik::kSkinMaxLdsBytes)) return rc;
 	if (int rc = check_mesh(bone_count, vertex_count, influences, positions, bone_indices, weights)) return rc;
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MBIK_ENODEV, "no HIP device visible");
 	if (device < 0 || device >= ndev) return fail(MBIK_EINVAL, "device index out of range");
 	std::unique_ptr<mbik_mesh> m(new mbik_mesh());
 	m->device = device, m->B = bone_count, m->V = vertex_count, m->K = influences, m->normals = normals != nullptr;
+	if (shaped) m->P = shapes->shape_count, m->mode = shapes->mode;
 	DeviceGuard guard(device);
 	int cus = 0;
 	if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) m->cu_count = cus;
 	if (vertex_count > 0) {
 		const mbik::SkinLayout l = mbik::skin_layout(vertex_count, influences, m->normals);
-		std::vector<unsigned char> packed((size_t)l.bytes);
+		const int64_t bytes = shaped ? mbik::morph_layout(vertex_count, influences, m->normals, m->P).bytes : l.bytes;
+		std::vector<unsigned char> packed((size_t)bytes);
 		mbik::skin_pack(vertex_count, influences, positions, normals, bone_indices, weights, packed.data());
+		if (shaped) mbik::morph_pack(vertex_count, influences, m->P, shapes->positions, shapes->normals, packed.data());
 		void *d = nullptr;
 		if (hipMalloc(&d, packed.size()) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc failed for the mesh");
 		m->d_mesh = static_cast<unsigned char *>(d);
@@ -120,6 +149,21 @@ int32_t mbik_mesh_create(int32_t bone_count, int32_t vertex_count, int32_t influ
 	}
 	*out_mesh = m.release();
 	return MBIK_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t mbik_mesh_create(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions, const float *normals,
+		const int32_t *bone_indices, const float *weights, int32_t device, mbik_mesh **out_mesh) {
+	return create_mesh(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, false, nullptr, device, out_mesh);
+}
+
+int32_t mbik_mesh_create_shaped(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
+		const float *normals, const int32_t *bone_indices, const float *weights, const mbik_mesh_shapes *shapes, int32_t device,
+		mbik_mesh **out_mesh) {
+	return create_mesh(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, true, shapes, device, out_mesh);
 }
 
 void mbik_mesh_destroy(mbik_mesh *m) {
@@ -134,7 +178,7 @@ void mbik_mesh_destroy(mbik_mesh *m) {
 int32_t mbik_mesh_launch_shape(const mbik_mesh *m, int32_t count, int32_t *skeletons_per_block, int32_t *vertex_chunks) {
 	if (!m) return fail(MBIK_EINVAL, "null mesh");
 	if (count < 0) return fail(MBIK_EINVAL, "negative count");
-	const SkinShape sh = shape_of(m, count);
+	const SkinShape sh = shape_of(m, count, m->P > 0);
 	if (skeletons_per_block) *skeletons_per_block = sh.S;
 	if (vertex_chunks) *vertex_chunks = sh.chunks;
 	return MBIK_OK;
@@ -146,10 +190,25 @@ int32_t mbik_skin_vertices(mbik_mesh *m, int32_t count, const float *skin, float
 	const int rc = check_call(m->B, m->V, m->normals, count, skin, out_positions, out_normals);
 	if (rc) return rc < 0 ? rc : MBIK_OK;
 	DeviceGuard guard(m->device);
-	const SkinShape sh = shape_of(m, count);
+	const SkinShape sh = shape_of(m, count, false);
 	hipError_t e = mbik::launch_skin(reinterpret_cast<hipStream_t>(hip_stream), m->K, count, m->B, m->V, sh.S, sh.chunk, sh.chunks,
 			sh.vshift, m->d_mesh, m->normals, skin, out_positions, out_normals);
 	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("skinning launch failed: ") + hipGetErrorString(e));
+	return MBIK_OK;
+}
+
+int32_t mbik_skin_vertices_shaped(mbik_mesh *m, int32_t count, const float *skin, const float *shape_weights, float *out_positions,
+		float *out_normals, void *hip_stream) {
+	if (!m) return fail(MBIK_EINVAL, "null mesh");
+	if (m->P < 1) return fail(MBIK_EINVAL, "the mesh has no shapes (mbik_mesh_create_shaped)");
+	const int rc = check_call(m->B, m->V, m->normals, count, skin, out_positions, out_normals);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	if (int rw = check_shape_weights(m->V, m->P, count, shape_weights, out_positions, out_normals)) return rw;
+	DeviceGuard guard(m->device);
+	const SkinShape sh = shape_of(m, count, true);
+	hipError_t e = mbik::launch_skin_shaped(reinterpret_cast<hipStream_t>(hip_stream), m->K, m->mode, count, m->B, m->V, m->P, sh.S,
+			sh.chunk, sh.chunks, sh.vshift, m->d_mesh, m->normals, skin, shape_weights, out_positions, out_normals);
+	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("shaped skinning launch failed: ") + hipGetErrorString(e));
 	return MBIK_OK;
 }
 
@@ -161,6 +220,19 @@ int32_t mbik_skin_vertices_cpu(int32_t bone_count, int32_t vertex_count, int32_t
 	if (rc) return rc < 0 ? rc : MBIK_OK;
 	mbik::skin_vertices_host(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, count, skin,
 			out_positions, out_normals);
+	return MBIK_OK;
+}
+
+int32_t mbik_skin_vertices_shaped_cpu(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
+		const float *normals, const int32_t *bone_indices, const float *weights, const mbik_mesh_shapes *shapes, int32_t count,
+		const float *skin, const float *shape_weights, float *out_positions, float *out_normals) {
+	if (int rc = check_mesh(bone_count, vertex_count, influences, positions, bone_indices, weights)) return rc;
+	if (int rc = check_shapes(bone_count, vertex_count, normals != nullptr, shapes, -1)) return rc;
+	const int rc = check_call(bone_count, vertex_count, normals != nullptr, count, skin, out_positions, out_normals);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	if (int rw = check_shape_weights(vertex_count, shapes->shape_count, count, shape_weights, out_positions, out_normals)) return rw;
+	mbik::morph_skin_vertices_host(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, shapes->shape_count,
+			shapes->mode, shapes->positions, shapes->normals, count, skin, shape_weights, out_positions, out_normals);
 	return MBIK_OK;
 }
 

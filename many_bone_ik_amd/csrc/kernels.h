@@ -172,6 +172,11 @@ hipError_t launch_fk(hipStream_t st, int count, int B, int P, int S, int levels,
 // by 256 >> vshift skeleton groups.  mesh is the device copy in skin_layout()'s planes; out_n null = positions only.
 hipError_t launch_skin(hipStream_t st, int K, int count, int B, int V, int S, int chunk, int chunks, int vshift,
 		const unsigned char *mesh, bool mesh_normals, const float *skin, float *out_p, float *out_n);
+// k_skin.hip: mbik_skin_vertices_shaped (morph.h).  The same grid and block; S * (B * 48 + P * 4) bytes of LDS a block (the
+// tile's shape weights behind its matrices); mesh carries morph_layout()'s shape planes behind skin_layout()'s; shape_weights
+// is device memory [count][P]; mode is a MorphMode.
+hipError_t launch_skin_shaped(hipStream_t st, int K, int mode, int count, int B, int V, int P, int S, int chunk, int chunks, int vshift,
+		const unsigned char *mesh, bool mesh_normals, const float *skin, const float *shape_weights, float *out_p, float *out_n);
 // k_blend.hip: mbik_pose_blend (blend.h).  One thread per bone of the total_bones = count * B, 256 bones a block, 20 KiB
 // of static LDS; influence_per_skeleton (device, [count]) overrides influence when given; pose_out may be pose_in or pose_mod.
 hipError_t launch_blend(hipStream_t st, int64_t total_bones, int B, int libm, float influence, const float *influence_per_skeleton,

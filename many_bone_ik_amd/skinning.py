@@ -6,6 +6,11 @@ takes device pointers -- the skin transforms are `Plan.pose_globals(..., inv_bin
 output -- and is asynchronous on the given HIP stream.  `skin_vertices_cpu()` runs the same code
 on numpy arrays without a device, and `synthetic_mesh()` is the seeded mesh generator the tests
 and tools/skin_bench.py use.
+
+Blend shapes (ABI 13): a `Mesh` created with `shape_positions` carries P shapes
+shared by every skeleton, `Mesh.skin(..., shape_weights_ptr=...)` morphs each skeleton by its own P
+weights in front of the skinning (mbik_skin_vertices_shaped), `skin_vertices_cpu(...,
+shape_weights=...)` is the host side and `synthetic_shapes()` the seeded generator.
 """
 from __future__ import annotations
 
@@ -33,28 +38,63 @@ def _mesh_arrays(positions, bone_indices, weights, normals):
     return pos, idx, wgt, nrm
 
 
+def _shape_arrays(V, shape_positions, shape_normals, shape_mode):
+    """-> (MbikMeshShapes, the arrays it points into), or (None, ()) without shapes."""
+    if shape_positions is None:
+        if shape_normals is not None:
+            raise ValueError("shape_normals without shape_positions")
+        return None, ()
+    if shape_mode not in _lib.SHAPE_MODES:
+        raise ValueError("shape_mode must be 'relative' or 'normalized'")
+    sp = np.ascontiguousarray(shape_positions, np.float32)
+    sn = None if shape_normals is None else np.ascontiguousarray(shape_normals, np.float32)
+    P = sp.shape[0]
+    assert sp.shape == (P, V, 3), sp.shape
+    assert sn is None or sn.shape == (P, V, 3), sn.shape
+    sh = _lib.MbikMeshShapes(C.sizeof(_lib.MbikMeshShapes), P, _lib.SHAPE_MODES[shape_mode], _ptr(sp), _ptr(sn))
+    return sh, (sp, sn)
+
+
 class Mesh:
     """One mesh surface on one GPU (mbik_mesh_create).  Immutable; close() frees it."""
 
-    def __init__(self, bone_count: int, positions, bone_indices, weights, normals=None, device: int = 0):
+    def __init__(self, bone_count: int, positions, bone_indices, weights, normals=None, device: int = 0,
+                 shape_positions=None, shape_normals=None, shape_mode: str = "relative"):
+        """shape_positions [P][V][3] (and shape_normals, exactly when `normals` is given) make a
+        shaped mesh (mbik_mesh_create_shaped); shape_mode is 'relative' or 'normalized'."""
         self._L = _lib.load()
         pos, idx, wgt, nrm = _mesh_arrays(positions, bone_indices, weights, normals)
         self.bone_count, self.vertex_count, self.influences = int(bone_count), pos.shape[0], idx.shape[1]
         self.has_normals = nrm is not None
         self.device = device
+        shapes, _keep = _shape_arrays(pos.shape[0], shape_positions, shape_normals, shape_mode)
+        self.shape_count = 0 if shapes is None else shapes.shape_count
         h = C.c_void_p()
-        check(self._L.mbik_mesh_create(self.bone_count, self.vertex_count, self.influences, _ptr(pos), _ptr(nrm), _ptr(idx),
-                                       _ptr(wgt), device, C.byref(h)))
+        if shapes is None:
+            check(self._L.mbik_mesh_create(self.bone_count, self.vertex_count, self.influences, _ptr(pos), _ptr(nrm), _ptr(idx),
+                                           _ptr(wgt), device, C.byref(h)))
+        else:
+            check(self._L.mbik_mesh_create_shaped(self.bone_count, self.vertex_count, self.influences, _ptr(pos), _ptr(nrm),
+                                                  _ptr(idx), _ptr(wgt), C.byref(shapes), device, C.byref(h)))
         self.h = h
 
-    def skin(self, skin_ptr: int, out_positions_ptr: int, count: int, out_normals_ptr: int = 0, stream: int = 0) -> None:
+    def skin(self, skin_ptr: int, out_positions_ptr: int, count: int, out_normals_ptr: int = 0, stream: int = 0,
+             shape_weights_ptr: int = 0) -> None:
         """mbik_skin_vertices: out_positions [count][vertices][3] (and out_normals) from the device
-        skin transforms [count][bones][12]; asynchronous on `stream`."""
+        skin transforms [count][bones][12]; asynchronous on `stream`.  With shape_weights_ptr (device,
+        [count][shapes]) mbik_skin_vertices_shaped: each skeleton morphed by its own weights first;
+        without it a shaped mesh skins its base arrays."""
+        if shape_weights_ptr:
+            check(self._L.mbik_skin_vertices_shaped(self.h, count, C.c_void_p(skin_ptr or None), C.c_void_p(shape_weights_ptr),
+                                                    C.c_void_p(out_positions_ptr or None), C.c_void_p(out_normals_ptr or None),
+                                                    C.c_void_p(stream or None)))
+            return
         check(self._L.mbik_skin_vertices(self.h, count, C.c_void_p(skin_ptr or None), C.c_void_p(out_positions_ptr or None),
                                          C.c_void_p(out_normals_ptr or None), C.c_void_p(stream or None)))
 
     def launch_shape(self, count: int) -> tuple[int, int]:
-        """(skeletons per block, vertex chunks) of a skin() call for `count` skeletons."""
+        """(skeletons per block, vertex chunks) of a skin() call for `count` skeletons; of the shaped
+        call when the mesh has shapes."""
         s, c = C.c_int32(0), C.c_int32(0)
         check(self._L.mbik_mesh_launch_shape(self.h, count, C.byref(s), C.byref(c)))
         return s.value, c.value
@@ -77,9 +117,11 @@ class Mesh:
             pass
 
 
-def skin_vertices_cpu(bone_count: int, positions, bone_indices, weights, skin, normals=None):
+def skin_vertices_cpu(bone_count: int, positions, bone_indices, weights, skin, normals=None, shape_positions=None,
+                      shape_normals=None, shape_mode: str = "relative", shape_weights=None):
     """mbik_skin_vertices_cpu (host only): `skin` [count][bones][12] -> (positions [count][V][3],
-    normals [count][V][3] or None when the mesh has none)."""
+    normals [count][V][3] or None when the mesh has none).  With shape_positions [P][V][3] (and
+    shape_normals) and shape_weights [count][P]: mbik_skin_vertices_shaped_cpu."""
     L = _lib.load()
     pos, idx, wgt, nrm = _mesh_arrays(positions, bone_indices, weights, normals)
     sk = np.ascontiguousarray(skin, np.float32)
@@ -87,6 +129,17 @@ def skin_vertices_cpu(bone_count: int, positions, bone_indices, weights, skin, n
     assert sk.shape == (count, bone_count, 12), sk.shape
     out_p = np.empty((count, V, 3), np.float32)
     out_n = None if nrm is None else np.empty((count, V, 3), np.float32)
+    shapes, _keep = _shape_arrays(V, shape_positions, shape_normals, shape_mode)
+    if shapes is not None:
+        if shape_weights is None:
+            raise ValueError("shape_positions without shape_weights")
+        cw = np.ascontiguousarray(shape_weights, np.float32)
+        assert cw.shape == (count, shapes.shape_count), cw.shape
+        check(L.mbik_skin_vertices_shaped_cpu(bone_count, V, idx.shape[1], _ptr(pos), _ptr(nrm), _ptr(idx), _ptr(wgt),
+                                              C.byref(shapes), count, _ptr(sk), _ptr(cw), _ptr(out_p), _ptr(out_n)))
+        return out_p, out_n
+    if shape_weights is not None:
+        raise ValueError("shape_weights without shape_positions")
     check(L.mbik_skin_vertices_cpu(bone_count, V, idx.shape[1], _ptr(pos), _ptr(nrm), _ptr(idx), _ptr(wgt), count, _ptr(sk),
                                    _ptr(out_p), _ptr(out_n)))
     return out_p, out_n
@@ -133,3 +186,24 @@ def synthetic_mesh(parents, rest_globals, vertex_count: int, influences: int, se
     raw = rng.uniform(0.25, 1.0, (V, influences)) * 0.5 ** np.arange(influences)
     weights = (raw / raw.sum(axis=1, keepdims=True)).astype(np.float32)
     return positions, normals, lists[bone], weights
+
+
+def synthetic_shapes(positions, normals, shape_count: int, seed: int):
+    """Seeded dense blend shapes for a mesh: (shape_positions [P][V][3], shape_normals [P][V][3], or
+    None when `normals` is None).  Position offsets are smooth in the vertex order (a few sine waves
+    of amplitude up to 0.05 per shape, as a body-shape or face slider moves neighbouring vertices
+    together) plus a little noise; normal offsets have magnitude at most 0.1."""
+    pos = np.asarray(positions, np.float32)
+    V, P = pos.shape[0], int(shape_count)
+    rng = np.random.default_rng(seed)
+    t = np.arange(V, dtype=np.float64)[None, :, None] / max(V, 1)
+    freq = rng.uniform(1.0, 8.0, (P, 1, 3))
+    phase = rng.uniform(0.0, 2.0 * np.pi, (P, 1, 3))
+    amp = rng.uniform(0.01, 0.05, (P, 1, 3))
+    sp = (amp * np.sin(2.0 * np.pi * freq * t + phase) + rng.normal(0.0, 0.002, (P, V, 3))).astype(np.float32)
+    if normals is None:
+        return sp, None
+    d = rng.normal(0.0, 1.0, (P, V, 3))
+    d /= np.maximum(np.linalg.norm(d, axis=2, keepdims=True), 1e-12)
+    sn = (d * rng.uniform(0.0, 0.1, (P, V, 1))).astype(np.float32)
+    return sp, sn
