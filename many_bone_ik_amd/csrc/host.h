@@ -29,74 +29,6 @@ using mbik::node_area_floats;
 using mbik::node_at;
 using mbik::TopoSlice;
 
-struct mbik_group {
-	std::vector<mbik_plan *> plans; // not owned
-	int device = 0;
-	void *d_plans = nullptr, *d_entries = nullptr;
-};
-
-struct mbik_plan {
-	mbik::HostPlan host;
-	int device = 0;
-	int lanes_override = 0, spw_override = 0, interval_override = 0;
-	int cu_count = 256;
-	std::vector<void *> allocs;
-	DevPlan dev{};
-	int64_t device_bytes = 0;
-	double alg_bytes = 0;
-	double alg_flops = 0;
-	int sched_K = -1, sched_c = -1, sched_staging = -1; // layout of the uploaded topology blob
-	int staging_override = -1;                           // mbik_plan_set_heading_staging; -1 = automatic
-	int tab64 = 0;                                       // mbik_plan_set_table_addressing
-	int locals_override = -1;                            // mbik_plan_set_locals_placement; -1 = automatic
-	int waves_override = -1;                             // mbik_plan_set_waves_per_simd; -1 = automatic
-	int helper_override = -1;                            // mbik_plan_set_helper_wave; -1 = automatic
-	int roles_override = -1;                             // mbik_plan_set_wave_roles; -1 = automatic (off until autotuned)
-	int sched_locals = -1, sched_roles = -1;
-	float *d_locals = nullptr;                           // [N][B][12] for state_hbm 1
-	float *d_state = nullptr;                            // [N][state stride] for state_hbm 2
-	size_t d_state_floats = 0;
-	float *d_gtile = nullptr;                            // state_hbm 2: checkpoint globals, skeleton-tiled
-	size_t d_gtile_floats = 0;
-	void *d_sched = nullptr; // topology blob (includes the lane schedule)
-	// scratch for mbik_solve_host
-	float *d_in = nullptr, *d_tg = nullptr, *d_out = nullptr;
-	size_t scratch_skel = 0;
-	// device copies of the setup tables (mbik_plan_rebuild_setup)
-	mbik::SetupView dsetup{};
-	bool dsetup_ready = false;
-	// constraint_mode: the persistent IKNode3D caches (cmode.h), lanes per skeleton (0 = auto)
-	CmodeState cm{};
-	int cm_lanes = 0;
-	int cm_spw_div = 0;                                  // constraint_mode: skeletons per wave = (64 / K) >> cm_spw_div
-	// the creation inputs, for mbik_plan_save (the topology is rebuilt from them on load)
-	std::vector<int32_t> src_parents;
-	std::vector<mbik_pin> src_pins;
-	std::vector<mbik_constraint> src_cons;
-	std::vector<float> src_bone_damp;
-	int32_t src_max_cones = 1;
-	mbik_config src_cfg{};
-	bool setup_on_device = false; // mbik_plan_create_device: the setup pose given to finish_plan is a device buffer
-	// skeleton-tiled copies of D / CF / CD for launches with the whole state in device memory
-	// (DevPlan::row_at); rebuilt when the tables changed since (tables_version)
-	float *d_Dt = nullptr, *d_CFt = nullptr;
-	double *d_CDt = nullptr;
-	int tables_version = 1, tiled_version = 0;
-	// the tiling's completion, for launches on another stream than the one that tiled
-	hipEvent_t tile_ev = nullptr;
-	hipStream_t tile_stream = nullptr;
-	bool tile_pending = false;
-	// helper-wave timeouts (DevPlan::help_flag): the plan's own host-mapped flag word, which a
-	// launch's kernel sets and the plan's next call reports (take_helper_timeout); the deadline
-	// override of mbik_plan_debug_helper (0: kHelpTimeoutMs)
-	unsigned int *help_flag = nullptr;
-	int help_timeout_us = 0;
-	// mbik_pose_globals: the device copy of the depth-ordered bone schedule (kernels.h launch_fk), built
-	// from src_parents / src_pins on the first call and owned through allocs
-	int *d_fk_sched = nullptr;
-	int fk_levels = 0;
-};
-
 namespace mbik_host {
 
 // The calling thread's last error message (mbik_last_error) and the error-return helper.
@@ -114,6 +46,134 @@ struct DeviceGuard {
 		if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
 	}
 };
+
+// One hipMalloc allocation and its size, owned: freed with the object that holds it, on the device
+// it was taken on.  The handles and every local scratch buffer of the host side own their device
+// memory through it; the device-side views (DevPlan, CmodeState, SetupView, ClipView) hold raw
+// pointers into these.
+class DevBuf {
+public:
+	DevBuf() = default;
+	DevBuf(DevBuf &&o) noexcept : p_(o.p_), bytes_(o.bytes_), device_(o.device_) { o.p_ = nullptr, o.bytes_ = 0; }
+	DevBuf &operator=(DevBuf &&o) noexcept {
+		std::swap(p_, o.p_), std::swap(bytes_, o.bytes_), std::swap(device_, o.device_);
+		return *this;
+	}
+	~DevBuf() { reset(); }
+	// Grow-only: leaves a buffer of at least `bytes` on the current device.  A larger one is
+	// allocated before the old one is freed, and its contents are undefined.  Fails with
+	// MBIK_ENOMEM and the text `what`, which names what was being allocated; the old buffer stays.
+	int reserve(size_t bytes, const char *what);
+	void reset();
+	size_t bytes() const { return bytes_; }
+	explicit operator bool() const { return p_ != nullptr; }
+	template <class T>
+	T *as() const { return static_cast<T *>(p_); }
+
+private:
+	void *p_ = nullptr;
+	size_t bytes_ = 0;
+	int device_ = 0;
+};
+
+// The layout settings a caller may pin (mbik_plan_set_*), saved with the plan, and what an
+// autotune may change: an autotune that fails, or that times nothing, copies the caller's back.
+struct LayoutPins {
+	int lanes = 0, spw = 0, interval = 0; // mbik_plan_set_launch / mbik_plan_set_layout; 0 = automatic
+	int staging = -1;                     // mbik_plan_set_heading_staging; -1 = automatic
+	int locals = -1;                      // mbik_plan_set_locals_placement; -1 = automatic
+	int waves = -1;                       // mbik_plan_set_waves_per_simd; -1 = automatic
+	int helper = -1;                      // mbik_plan_set_helper_wave; -1 = automatic
+	int roles = -1;                       // mbik_plan_set_wave_roles; -1 = automatic (off until autotuned)
+	int cm_lanes = 0;                     // constraint_mode: lanes per skeleton (0 = auto)
+	int cm_spw_div = 0;                   // constraint_mode: skeletons per wave = (64 / K) >> cm_spw_div
+};
+
+} // namespace mbik_host
+
+struct mbik_group {
+	std::vector<mbik_plan *> plans; // not owned
+	int device = 0;
+	mbik_host::DevBuf d_plans, d_entries;
+};
+
+struct mbik_plan {
+	mbik_plan() = default;
+	mbik_plan(const mbik_plan &) = delete;
+	mbik_plan &operator=(const mbik_plan &) = delete;
+	~mbik_plan(); // the event and the host-mapped flag word; every buffer frees itself
+
+	mbik::HostPlan host;
+	int device = 0;
+	mbik_host::LayoutPins pins;
+	int cu_count = 256;
+	DevPlan dev{};
+	// device memory counted: the table uploads, locals, state, checkpoint globals, the tiled
+	// tables, constraint_mode's node caches and dirty words, the fk schedule; not the topology
+	// blob, the mbik_solve_host scratch or the flag word
+	int64_t device_bytes = 0;
+	double alg_bytes = 0;
+	double alg_flops = 0;
+	int sched_K = -1, sched_c = -1, sched_staging = -1; // layout of the uploaded topology blob
+	int tab64 = 0;                                       // mbik_plan_set_table_addressing
+	int sched_locals = -1, sched_roles = -1;
+	// tables uploaded once and never resized: D / CF / CD, constraint_mode's pre-order tables, the
+	// setup view's (mbik_plan_rebuild_setup); dev, cm and dsetup point into them
+	std::vector<mbik_host::DevBuf> uploads;
+	mbik_host::DevBuf locals;                            // [N][B][12] for state_hbm 1
+	mbik_host::DevBuf state;                             // [N][state stride] for state_hbm 2
+	mbik_host::DevBuf gtile;                             // state_hbm 2: checkpoint globals, skeleton-tiled
+	mbik_host::DevBuf topo; // topology blob (includes the lane schedule)
+	// scratch for mbik_solve_host
+	mbik_host::DevBuf h_in, h_tg, h_out;
+	size_t scratch_skel = 0;
+	// device copies of the setup tables (mbik_plan_rebuild_setup)
+	mbik::SetupView dsetup{};
+	bool dsetup_ready = false;
+	// constraint_mode: the persistent IKNode3D caches (cmode.h)
+	CmodeState cm{};
+	mbik_host::DevBuf cm_node, cm_dirty;
+	// the creation inputs, for mbik_plan_save (the topology is rebuilt from them on load)
+	std::vector<int32_t> src_parents;
+	std::vector<mbik_pin> src_pins;
+	std::vector<mbik_constraint> src_cons;
+	std::vector<float> src_bone_damp;
+	int32_t src_max_cones = 1;
+	mbik_config src_cfg{};
+	bool setup_on_device = false; // mbik_plan_create_device: the setup pose given to finish_plan is a device buffer
+	// skeleton-tiled copies of D / CF / CD for launches with the whole state in device memory
+	// (DevPlan::row_at); rebuilt when the tables changed since (tables_version)
+	mbik_host::DevBuf Dt, CFt, CDt;
+	int tables_version = 1, tiled_version = 0;
+	// the tiling's completion, for launches on another stream than the one that tiled
+	hipEvent_t tile_ev = nullptr;
+	hipStream_t tile_stream = nullptr;
+	bool tile_pending = false;
+	// helper-wave timeouts (DevPlan::help_flag): the plan's own host-mapped flag word, which a
+	// launch's kernel sets and the plan's next call reports (take_helper_timeout); the deadline
+	// override of mbik_plan_debug_helper (0: kHelpTimeoutMs)
+	unsigned int *help_flag = nullptr;
+	int help_timeout_us = 0;
+	// mbik_pose_globals: the device copy of the depth-ordered bone schedule (kernels.h launch_fk), built
+	// from src_parents / src_pins on the first call
+	mbik_host::DevBuf fk_sched;
+	int fk_levels = 0;
+#ifdef MBIK_REPLAY
+	mbik_host::DevBuf rec_dump; // mbik_debug_replay's records (DevPlan::rec_dump)
+#endif
+};
+
+namespace mbik_host {
+
+// MBIK_OK, or MBIK_ENODEV "no HIP device visible" / MBIK_EINVAL with `out_of_range`.
+int check_device(int device, const char *out_of_range = "device index out of range");
+// The device's compute units (256 where the query fails).
+int cu_count_of(int device);
+// Whether the byte ranges [a, a + na) and [b, b + nb) share a byte.
+inline bool overlap(const void *a, size_t na, const void *b, size_t nb) {
+	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+	return x < y + nb && y < x + na;
+}
 
 // device-memory areas addressed through buffer resources (32-bit byte offsets): the state of
 // placements 1 and 2, and the setup tables of every layout that can (kTab32 / kTabTiled)
@@ -133,6 +193,9 @@ struct CmShape {
 };
 CmShape cmode_shape_of(const mbik_plan *p, int64_t count);
 size_t cmode_lds_bytes(const mbik_plan *p, CmShape sh);
+// constraint_mode state in device memory and in a plan file: node caches, then dirty words
+size_t cmode_node_bytes(const mbik::HostPlan &h);
+size_t cmode_dirty_bytes(const mbik::HostPlan &h);
 size_t cmode_file_node_bytes(const mbik::HostPlan &h);
 std::vector<float> cmode_nodes_tiled(const mbik::HostPlan &h, const float *plain);
 void cmode_nodes_plain(const mbik::HostPlan &h, const float *tiled, float *plain);

@@ -10,28 +10,6 @@
 using namespace mbik_host;
 
 namespace {
-// The layout settings a caller may pin, and what an autotune may change.  An autotune that fails,
-// or that times nothing (no eligible candidate), leaves them as the caller set them.
-struct Overrides {
-	int lanes, spw, interval, staging, locals, waves, helper, roles, cm_lanes, cm_spw_div;
-};
-Overrides save_overrides(const mbik_plan *p) {
-	return Overrides{p->lanes_override, p->spw_override, p->interval_override, p->staging_override, p->locals_override,
-			p->waves_override, p->helper_override, p->roles_override, p->cm_lanes, p->cm_spw_div};
-}
-void restore_overrides(mbik_plan *p, const Overrides &o) {
-	p->lanes_override = o.lanes;
-	p->spw_override = o.spw;
-	p->interval_override = o.interval;
-	p->staging_override = o.staging;
-	p->locals_override = o.locals;
-	p->waves_override = o.waves;
-	p->helper_override = o.helper;
-	p->roles_override = o.roles;
-	p->cm_lanes = o.cm_lanes;
-	p->cm_spw_div = o.cm_spw_div;
-	p->sched_K = -1;
-}
 constexpr int kNothingTimed = 1; // (internal: no candidate was eligible)
 } // namespace
 static int autotune_layouts(mbik_plan *p, int first, int count, const float *pose_in, const float *targets, float *pose_out,
@@ -44,17 +22,15 @@ extern "C" {
 // put back: the caller's next frame sees the caches as they were.
 static int cmode_autotune(mbik_plan *p, int first, int count, const float *pose_in, const float *targets, float *pose_out,
 		hipStream_t st) {
-	if (p->lanes_override) return MBIK_OK; // pinned by mbik_plan_set_launch / set_layout
+	if (p->pins.lanes) return MBIK_OK; // pinned by mbik_plan_set_launch / set_layout
 	mbik::HostPlan &h = p->host;
 	// candidates: 1, 2, 4, ... up to the widest sibling level's power of two (the default K)
 	mbik::build_schedule(h, 0, count, 0, 0, blocks_per_cu, p, p->cu_count);
 	const int max_lanes = h.K;
-	const size_t N = (size_t)h.N;
-	const size_t node_bytes = node_area_floats(3 * h.B + 2 * h.NC, N) * sizeof(float);
-	const size_t dirty_bytes = 4 * (size_t)p->cm.W * N * sizeof(uint32_t);
-	void *save = nullptr;
-	if (hipMalloc(&save, node_bytes + dirty_bytes) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc autotune state copy");
-	char *sv = static_cast<char *>(save);
+	const size_t node_bytes = cmode_node_bytes(h), dirty_bytes = cmode_dirty_bytes(h);
+	DevBuf save;
+	if (int rc = save.reserve(node_bytes + dirty_bytes, "hipMalloc autotune state copy")) return rc;
+	char *sv = save.as<char>();
 	auto copy = [&](bool to_save) {
 		hipError_t a = to_save ? hipMemcpyAsync(sv, p->cm.node, node_bytes, hipMemcpyDeviceToDevice, st)
 							   : hipMemcpyAsync(p->cm.node, sv, node_bytes, hipMemcpyDeviceToDevice, st);
@@ -63,17 +39,14 @@ static int cmode_autotune(mbik_plan *p, int first, int count, const float *pose_
 		return a == hipSuccess && b == hipSuccess ? MBIK_OK : fail(MBIK_EHIP, "hipMemcpyAsync autotune state");
 	};
 	hipEvent_t e0, e1;
-	if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-		(void)hipFree(save);
-		return fail(MBIK_EHIP, "hipEventCreate");
-	}
+	if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fail(MBIK_EHIP, "hipEventCreate");
 	int rc = copy(true);
 	float best_ms = 0.0f;
 	int best = 0, best_div = 0, best_rw = 0;
 	// classic: lanes per skeleton x skeletons per wave (full waves, or half: twice the waves per
 	// SIMD for the node-cache misses to overlap); wave roles (cmode.h mbik_cmode_kernel_rw, plans
 	// without stabilization, unless pinned off): 2, 4 or 8 roles x 64, 32 or 16 skeletons per block
-	const int roles0 = p->roles_override;
+	const int roles0 = p->pins.roles;
 	std::vector<std::array<int, 3>> cands; // lanes, spw div, wave roles
 	if (roles0 != 1)
 		for (int lanes = 1; lanes <= max_lanes && lanes <= 64; lanes <<= 1)
@@ -83,9 +56,9 @@ static int cmode_autotune(mbik_plan *p, int first, int count, const float *pose_
 			for (int div = 0; div < 3; div++) cands.push_back({lanes, div, 1});
 	for (size_t ci = 0; ci < cands.size() && rc == MBIK_OK; ci++) {
 		const int lanes = cands[ci][0], div = cands[ci][1];
-		p->cm_lanes = lanes;
-		p->cm_spw_div = div;
-		p->roles_override = cands[ci][2];
+		p->pins.cm_lanes = lanes;
+		p->pins.cm_spw_div = div;
+		p->pins.roles = cands[ci][2];
 		if ((rc = ensure_schedule(p, count)) != MBIK_OK) break;
 		if (cands[ci][2] && !h.cm_roles) continue; // (not eligible: 64-bit addressing)
 		float ms = 0.0f;
@@ -110,12 +83,11 @@ static int cmode_autotune(mbik_plan *p, int first, int count, const float *pose_
 	if (rc == MBIK_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(MBIK_EHIP, "hipStreamSynchronize");
 	(void)hipEventDestroy(e0);
 	(void)hipEventDestroy(e1);
-	(void)hipFree(save);
 	if (rc != MBIK_OK) return rc;
 	if (best == 0) return kNothingTimed;
-	p->cm_lanes = best;
-	p->cm_spw_div = best_div;
-	p->roles_override = best_rw;
+	p->pins.cm_lanes = best;
+	p->pins.cm_spw_div = best_div;
+	p->pins.roles = best_rw;
 	return ensure_schedule(p, count);
 }
 
@@ -124,11 +96,11 @@ static int cmode_autotune(mbik_plan *p, int first, int count, const float *pose_
 // The helper's second wave needs a free SIMD: at most two blocks of it per CU.
 static int autotune_helper(mbik_plan *p, int first, int count, const float *pose_in, const float *targets, float *pose_out,
 		hipStream_t st) {
-	if (p->helper_override != -1) return MBIK_OK;
-	p->helper_override = 1;
+	if (p->pins.helper != -1) return MBIK_OK;
+	p->pins.helper = 1;
 	const int64_t blocks = (count + p->host.spw - 1) / p->host.spw;
 	if (!helper_on(p) || blocks > 2 * (int64_t)p->cu_count) {
-		p->helper_override = 0;
+		p->pins.helper = 0;
 		return MBIK_OK;
 	}
 	hipEvent_t e0, e1;
@@ -136,7 +108,7 @@ static int autotune_helper(mbik_plan *p, int first, int count, const float *pose
 	float ms[2] = {0.0f, 0.0f};
 	int rc = MBIK_OK;
 	for (int h = 0; h < 2 && rc == MBIK_OK; h++) {
-		p->helper_override = h;
+		p->pins.helper = h;
 		if ((rc = launch(p, first, count, pose_in, targets, pose_out, st, p->host.iterations, 0, p->host.NS - 1)) != MBIK_OK) break;
 		(void)hipEventRecord(e0, st);
 		for (int r = 0; r < 3 && rc == MBIK_OK; r++)
@@ -148,7 +120,7 @@ static int autotune_helper(mbik_plan *p, int first, int count, const float *pose
 	(void)hipEventDestroy(e0);
 	(void)hipEventDestroy(e1);
 	if (rc == MBIK_OK) rc = take_helper_timeout(p);
-	p->helper_override = rc == MBIK_OK && ms[1] * 1.015f < ms[0] ? 1 : 0;
+	p->pins.helper = rc == MBIK_OK && ms[1] * 1.015f < ms[0] ? 1 : 0;
 	return rc;
 }
 
@@ -165,19 +137,21 @@ int32_t mbik_plan_autotune(mbik_plan *p, int32_t first, int32_t count, const flo
 	}
 	DeviceGuard guard(p->device);
 	hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-	const Overrides o0 = save_overrides(p);
+	const LayoutPins pins0 = p->pins; // an autotune that fails, or that times nothing, leaves them as the caller set them
 	int rc = p->host.constraint_mode ? cmode_autotune(p, first, count, pose_in, targets, pose_out, st)
 									 : autotune_layouts(p, first, count, pose_in, targets, pose_out, st);
 	if (rc == kNothingTimed) {
 		// nothing eligible was timed (e.g. wave roles pinned on a plan that cannot have them):
 		// the caller's settings stand
-		restore_overrides(p, o0);
+		p->pins = pins0;
+		p->sched_K = -1;
 		return ensure_schedule(p, count);
 	}
 	if (rc != MBIK_OK) {
 		// a candidate failed: the plan goes back to the caller's settings, and the error stands
 		const std::string err = g_err;
-		restore_overrides(p, o0);
+		p->pins = pins0;
+		p->sched_K = -1;
 		(void)ensure_schedule(p, count);
 		g_err = err;
 	}
@@ -189,24 +163,24 @@ int32_t mbik_plan_autotune(mbik_plan *p, int32_t first, int32_t count, const flo
 // The layout search of mbik_plan_autotune (plans without constraint_mode).
 static int autotune_layouts(mbik_plan *p, int first, int count, const float *pose_in, const float *targets, float *pose_out,
 		hipStream_t st) {
-	const int lanes = p->lanes_override;
-	const int staging0 = p->staging_override;
-	const int locals0 = p->locals_override;
-	const int waves0 = p->waves_override;
-	const int roles0 = p->roles_override;
+	const int lanes = p->pins.lanes;
+	const int staging0 = p->pins.staging;
+	const int locals0 = p->pins.locals;
+	const int waves0 = p->pins.waves;
+	const int roles0 = p->pins.roles;
 	if (roles0 != 1) {
 		// A launch whose skeletons are all resident at the default layout is bound by one
 		// skeleton's dependency chain; no layout shortens that, so there is nothing to time.
-		p->spw_override = 0;
-		p->interval_override = 0;
-		p->staging_override = staging0 < 0 ? 1 : staging0;
-		p->locals_override = locals0 < 0 ? 0 : locals0;
-		p->waves_override = waves0 < 0 ? 1 : waves0;
-		p->roles_override = 0;
+		p->pins.spw = 0;
+		p->pins.interval = 0;
+		p->pins.staging = staging0 < 0 ? 1 : staging0;
+		p->pins.locals = locals0 < 0 ? 0 : locals0;
+		p->pins.waves = waves0 < 0 ? 1 : waves0;
+		p->pins.roles = 0;
 		int rc0 = ensure_schedule(p, count);
 		if (rc0 != MBIK_OK) return rc0;
 		if ((int64_t)blocks_per_cu(p, p->host.lds_block_bytes) * p->host.spw * p->cu_count >= count && p->host.g_interval == 1) {
-			p->roles_override = roles0 < 0 ? 0 : roles0;
+			p->pins.roles = roles0 < 0 ? 0 : roles0;
 			return autotune_helper(p, first, count, pose_in, targets, pose_out, st);
 		}
 	}
@@ -300,13 +274,13 @@ static int autotune_layouts(mbik_plan *p, int first, int count, const float *pos
 	};
 	std::vector<Timed> timed;
 	for (auto [spw, c, stg, lh, ln, wv, rw] : cands) {
-		p->spw_override = spw;
-		p->interval_override = c;
-		p->lanes_override = ln;
-		p->staging_override = stg;
-		p->locals_override = lh;
-		p->waves_override = wv;
-		p->roles_override = rw;
+		p->pins.spw = spw;
+		p->pins.interval = c;
+		p->pins.lanes = ln;
+		p->pins.staging = stg;
+		p->pins.locals = lh;
+		p->pins.waves = wv;
+		p->pins.roles = rw;
 		if ((rc = ensure_schedule(p, count)) != MBIK_OK) {
 			// a placement this batch cannot have (device memory, or the 4 GiB buffer limit) is skipped
 			if (rc == MBIK_ENOMEM || rc == MBIK_EUNSUPPORTED) {
@@ -353,12 +327,12 @@ static int autotune_layouts(mbik_plan *p, int first, int count, const float *pos
 			best_rw = c.rw;
 			break;
 		}
-	p->roles_override = best_rw;
-	p->spw_override = best_spw;
-	p->interval_override = best_c;
-	p->staging_override = best_stg;
-	p->locals_override = best_lh;
-	p->lanes_override = best_ln;
-	p->waves_override = best_wv;
+	p->pins.roles = best_rw;
+	p->pins.spw = best_spw;
+	p->pins.interval = best_c;
+	p->pins.staging = best_stg;
+	p->pins.locals = best_lh;
+	p->pins.lanes = best_ln;
+	p->pins.waves = best_wv;
 	return ensure_schedule(p, count);
 }

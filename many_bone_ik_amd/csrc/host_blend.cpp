@@ -10,19 +10,14 @@ using namespace mbik_host;
 
 namespace {
 
-bool overlap(const void *a, const void *b, size_t n) {
-	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-	return x < y + n && y < x + n;
-}
-
 // The checks both entry points share, for count > 0 and B > 0.  Returns 0, or the error code.
 int check_args(int32_t count, int B, const float *pose_in, const float *pose_mod, const float *pose_out) {
 	if (!pose_in) return fail(MBIK_EINVAL, "null pose_in");
 	if (!pose_mod) return fail(MBIK_EINVAL, "null pose_mod");
 	if (!pose_out) return fail(MBIK_EINVAL, "null pose_out");
 	const size_t n = (size_t)count * B * 10 * sizeof(float);
-	if (pose_out != pose_in && overlap(pose_out, pose_in, n)) return fail(MBIK_EINVAL, "pose_out overlaps pose_in without being pose_in");
-	if (pose_out != pose_mod && overlap(pose_out, pose_mod, n))
+	if (pose_out != pose_in && overlap(pose_out, n, pose_in, n)) return fail(MBIK_EINVAL, "pose_out overlaps pose_in without being pose_in");
+	if (pose_out != pose_mod && overlap(pose_out, n, pose_mod, n))
 		return fail(MBIK_EINVAL, "pose_out overlaps pose_mod without being pose_mod");
 	return MBIK_OK;
 }

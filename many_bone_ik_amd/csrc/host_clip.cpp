@@ -13,8 +13,8 @@ using namespace mbik_host;
 struct mbik_clipset {
 	int device = 0;
 	int32_t B = 0, clip_count = 0, libm = 0;
-	unsigned char *d_blob = nullptr;
-	mbik::ClipView view{}; // device pointers into d_blob
+	DevBuf blob;
+	mbik::ClipView view{}; // device pointers into blob
 };
 
 namespace {
@@ -107,9 +107,7 @@ int32_t mbik_clipset_create(int32_t bone_count, const float *rest_pose, int32_t 
 	*out = nullptr;
 	Packed pk;
 	if (int rc = pack(bone_count, rest_pose, clip_count, clips, libm_variant, pk)) return rc;
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MBIK_ENODEV, "no HIP device visible");
-	if (device < 0 || device >= ndev) return fail(MBIK_EINVAL, "device index out of range");
+	if (int rc = check_device(device)) return rc;
 	std::unique_ptr<mbik_clipset> s(new mbik_clipset());
 	s->device = device, s->B = bone_count, s->clip_count = clip_count, s->libm = libm_variant;
 	// one blob: clip infos, headers, times, values, rest pose, each from a 16-byte boundary
@@ -125,14 +123,9 @@ int32_t mbik_clipset_create(int32_t bone_count, const float *rest_pose, int32_t 
 	if (n_val) std::memcpy(blob.data() + o_val, pk.values.data(), n_val);
 	if (n_rest) std::memcpy(blob.data() + o_rest, pk.rest.data(), n_rest);
 	DeviceGuard guard(device);
-	void *d = nullptr;
-	if (hipMalloc(&d, bytes) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc failed for the clip set");
-	if (hipMemcpy(d, blob.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
-		(void)hipFree(d);
-		return fail(MBIK_EHIP, "hipMemcpy failed for the clip set");
-	}
-	unsigned char *b = static_cast<unsigned char *>(d);
-	s->d_blob = b;
+	if (int rc = s->blob.reserve(bytes, "hipMalloc failed for the clip set")) return rc;
+	unsigned char *b = s->blob.as<unsigned char>();
+	if (hipMemcpy(b, blob.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(MBIK_EHIP, "hipMemcpy failed for the clip set");
 	s->view = mbik::ClipView{bone_count, clip_count, reinterpret_cast<const mbik::ClipInfo *>(b + o_info),
 			reinterpret_cast<const mbik::ClipHeader *>(b + o_head), reinterpret_cast<const double *>(b + o_time),
 			reinterpret_cast<const mbik::ClipValue *>(b + o_val), reinterpret_cast<const float *>(b + o_rest)};
@@ -140,14 +133,7 @@ int32_t mbik_clipset_create(int32_t bone_count, const float *rest_pose, int32_t 
 	return MBIK_OK;
 }
 
-void mbik_clipset_destroy(mbik_clipset *s) {
-	if (!s) return;
-	if (s->d_blob) {
-		DeviceGuard guard(s->device);
-		(void)hipFree(s->d_blob);
-	}
-	delete s;
-}
+void mbik_clipset_destroy(mbik_clipset *s) { delete s; }
 
 int32_t mbik_clip_sample(mbik_clipset *s, int32_t count, const double *time, const int32_t *clip_index, int32_t clip, float *pose_out,
 		void *hip_stream) {

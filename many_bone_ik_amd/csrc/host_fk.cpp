@@ -15,11 +15,6 @@ namespace {
 constexpr int64_t kFkBlockLdsTarget = 20 * 1024;
 constexpr int kFkMaxSkeletonsPerBlock = 64;
 
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-	return x < y + nb && y < x + na;
-}
-
 // The checks both entry points share; P = the rig's pin count.  Returns 0, or the error code.
 int check_args(int32_t count, int B, int P, const float *pose, const float *globals, const float *targets,
 		const float *pin_distance) {
@@ -33,7 +28,7 @@ int check_args(int32_t count, int B, int P, const float *pose, const float *glob
 
 // Builds the plan's schedule and uploads it (kernels.h launch_fk's layout); once per plan.
 int ensure_fk_schedule(mbik_plan *p) {
-	if (p->d_fk_sched) return MBIK_OK;
+	if (p->fk_sched) return MBIK_OK;
 	const int B = p->host.B, P = p->host.P;
 	if ((int)p->src_parents.size() != B || (int)p->src_pins.size() != P) return fail(MBIK_EINVAL, "plan without its rig description");
 	std::vector<int32_t> depth(B), order(B), level_off(B + 1);
@@ -49,14 +44,14 @@ int ensure_fk_schedule(mbik_plan *p) {
 		if (p->src_pins[e].bone < 0 || p->src_pins[e].bone >= B) return fail(MBIK_EINVAL, "pin bone out of range");
 		blob.push_back(p->src_pins[e].bone);
 	}
-	void *d = nullptr;
-	if (hipMalloc(&d, blob.size() * sizeof(int32_t)) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc failed for the bone schedule");
-	p->allocs.push_back(d);
-	if (hipMemcpy(d, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
+	// published only once the copy succeeded: a failed call leaves nothing behind
+	DevBuf d;
+	if (int rc = d.reserve(blob.size() * sizeof(int32_t), "hipMalloc failed for the bone schedule")) return rc;
+	if (hipMemcpy(d.as<void>(), blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
 		return fail(MBIK_EHIP, "hipMemcpy failed for the bone schedule");
-	p->device_bytes += (int64_t)(blob.size() * sizeof(int32_t));
+	p->device_bytes += (int64_t)d.bytes();
 	p->fk_levels = levels;
-	p->d_fk_sched = static_cast<int *>(d);
+	p->fk_sched = std::move(d);
 	return MBIK_OK;
 }
 
@@ -80,7 +75,7 @@ int32_t mbik_pose_globals(mbik_plan *p, int32_t count, const float *pose, const 
 	if (int rc = ensure_fk_schedule(p)) return rc;
 	const int64_t per = mbik::fk_lds_floats(B, 1) * (int64_t)sizeof(float);
 	const int S = (int)std::max<int64_t>(1, std::min<int64_t>({kFkBlockLdsTarget / per, kFkMaxSkeletonsPerBlock, count}));
-	hipError_t e = mbik::launch_fk(reinterpret_cast<hipStream_t>(hip_stream), count, B, P, S, p->fk_levels, p->d_fk_sched, pose,
+	hipError_t e = mbik::launch_fk(reinterpret_cast<hipStream_t>(hip_stream), count, B, P, S, p->fk_levels, p->fk_sched.as<int>(), pose,
 			inv_bind, globals, targets, pin_distance);
 	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("pose globals launch failed: ") + hipGetErrorString(e));
 	return MBIK_OK;

@@ -17,7 +17,7 @@ struct mbik_multi {
 		hipStream_t stream = nullptr;
 		hipEvent_t done = nullptr;
 		bool staged = false;
-		float *in = nullptr, *tg = nullptr, *out = nullptr; // staging on the plan's device
+		DevBuf in, tg, out; // staging on the plan's device
 	};
 	std::vector<Shard> sh;
 	hipEvent_t start = nullptr; // on the root device: "the caller's queued work is done"
@@ -28,10 +28,7 @@ void mbik_multi_destroy(mbik_multi *m) {
 	for (size_t i = 0; i < m->sh.size(); i++) {
 		auto &s = m->sh[i];
 		DeviceGuard g(m->plans[i]->device);
-		if (s.stream) (void)hipStreamSynchronize(s.stream);
-		if (s.in) (void)hipFree(s.in);
-		if (s.tg) (void)hipFree(s.tg);
-		if (s.out) (void)hipFree(s.out);
+		if (s.stream) (void)hipStreamSynchronize(s.stream); // (the staging is freed with the handle, below)
 		if (s.done) (void)hipEventDestroy(s.done);
 		if (s.stream) (void)hipStreamDestroy(s.stream);
 	}
@@ -46,9 +43,7 @@ int32_t mbik_multi_create(mbik_plan *const *plans, int32_t n_plans, int32_t root
 	if (!plans || n_plans <= 0 || !out) return fail(MBIK_EINVAL, "null argument or no plans");
 	if (flags & ~MBIK_MULTI_STAGE_ALL) return fail(MBIK_EINVAL, "unknown mbik_multi flags");
 	*out = nullptr;
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MBIK_ENODEV, "no HIP device visible");
-	if (root_device < 0 || root_device >= ndev) return fail(MBIK_EINVAL, "root device out of range");
+	if (int rc = check_device(root_device, "root device out of range")) return rc;
 	for (int i = 0; i < n_plans; i++) {
 		if (!plans[i]) return fail(MBIK_EINVAL, "null plan");
 		for (int j = 0; j < i; j++)
@@ -100,10 +95,10 @@ int32_t mbik_multi_create(mbik_plan *const *plans, int32_t n_plans, int32_t root
 			}
 		}
 		const size_t n = (size_t)p->host.N;
-		if (hipMalloc(&s.in, std::max<size_t>(1, n * B * 10) * sizeof(float)) != hipSuccess ||
-				hipMalloc(&s.tg, std::max<size_t>(1, n * P * 12) * sizeof(float)) != hipSuccess ||
-				hipMalloc(&s.out, std::max<size_t>(1, n * B * 10) * sizeof(float)) != hipSuccess)
-			return fail(MBIK_ENOMEM, "hipMalloc multi staging");
+		if (s.in.reserve(std::max<size_t>(1, n * B * 10) * sizeof(float), "hipMalloc multi staging") ||
+				s.tg.reserve(std::max<size_t>(1, n * P * 12) * sizeof(float), "hipMalloc multi staging") ||
+				s.out.reserve(std::max<size_t>(1, n * B * 10) * sizeof(float), "hipMalloc multi staging"))
+			return MBIK_ENOMEM;
 	}
 	*out = m.release();
 	return MBIK_OK;
@@ -144,12 +139,13 @@ int32_t mbik_multi_solve(mbik_multi *m, const float *pose_in, const float *targe
 		const float *in = pose_in + o * B * 10, *tg = targets ? targets + o * P * 12 : nullptr;
 		float *outp = pose_out + o * B * 10;
 		if (s.staged && n) {
-			if (hipMemcpyPeerAsync(s.in, p->device, in, m->root, n * B * 10 * sizeof(float), s.stream) != hipSuccess ||
-					(P > 0 && hipMemcpyPeerAsync(s.tg, p->device, tg, m->root, n * P * 12 * sizeof(float), s.stream) != hipSuccess))
+			float *s_in = s.in.as<float>(), *s_tg = s.tg.as<float>(), *s_out = s.out.as<float>();
+			if (hipMemcpyPeerAsync(s_in, p->device, in, m->root, n * B * 10 * sizeof(float), s.stream) != hipSuccess ||
+					(P > 0 && hipMemcpyPeerAsync(s_tg, p->device, tg, m->root, n * P * 12 * sizeof(float), s.stream) != hipSuccess))
 				rc = fail(MBIK_EHIP, "hipMemcpyPeerAsync (scatter)");
-			else if ((rc = mbik_solve(p, 0, (int32_t)n, s.in, s.tg, s.out, s.stream)) != MBIK_OK)
+			else if ((rc = mbik_solve(p, 0, (int32_t)n, s_in, s_tg, s_out, s.stream)) != MBIK_OK)
 				;
-			else if (hipMemcpyPeerAsync(outp, m->root, s.out, p->device, n * B * 10 * sizeof(float), s.stream) != hipSuccess)
+			else if (hipMemcpyPeerAsync(outp, m->root, s_out, p->device, n * B * 10 * sizeof(float), s.stream) != hipSuccess)
 				rc = fail(MBIK_EHIP, "hipMemcpyPeerAsync (gather)");
 		} else if (n) {
 			rc = mbik_solve(p, 0, (int32_t)n, in, tg, outp, s.stream);

@@ -17,16 +17,52 @@ int fail(int code, const std::string &msg) {
 	return code;
 }
 
+int DevBuf::reserve(size_t bytes, const char *what) {
+	if (p_ && bytes <= bytes_) return MBIK_OK;
+	void *a = nullptr;
+	if (hipMalloc(&a, bytes) != hipSuccess) return fail(MBIK_ENOMEM, what);
+	reset();
+	p_ = a;
+	bytes_ = bytes;
+	if (hipGetDevice(&device_) != hipSuccess) device_ = 0;
+	return MBIK_OK;
+}
+void DevBuf::reset() {
+	if (p_) {
+		DeviceGuard guard(device_);
+		(void)hipFree(p_);
+	}
+	p_ = nullptr;
+	bytes_ = 0;
+}
+
+int check_device(int device, const char *out_of_range) {
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MBIK_ENODEV, "no HIP device visible");
+	if (device < 0 || device >= ndev) return fail(MBIK_EINVAL, out_of_range);
+	return MBIK_OK;
+}
+int cu_count_of(int device) {
+	int cus = 0;
+	return hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0 ? cus : 256;
+}
+
+// Grows one of the plan's counted buffers (mbik_plan::device_bytes follows its size).
+static int reserve_counted(mbik_plan *p, DevBuf &b, size_t bytes, const char *what) {
+	const size_t old = b.bytes();
+	if (int rc = b.reserve(bytes, what)) return rc;
+	p->device_bytes += (int64_t)b.bytes() - (int64_t)old;
+	return MBIK_OK;
+}
+
 template <typename T>
 int upload(mbik_plan *p, const std::vector<T> &v, const T *&dst) {
-	size_t n = std::max<size_t>(1, v.size());
-	void *d = nullptr;
-	if (hipMalloc(&d, n * sizeof(T)) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc failed for plan table");
-	p->allocs.push_back(d);
-	p->device_bytes += (int64_t)(n * sizeof(T));
-	if (!v.empty() && hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
+	DevBuf b;
+	if (int rc = reserve_counted(p, b, std::max<size_t>(1, v.size()) * sizeof(T), "hipMalloc failed for plan table")) return rc;
+	if (!v.empty() && hipMemcpy(b.as<void>(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
 		return fail(MBIK_EHIP, "hipMemcpy failed for plan table");
-	dst = reinterpret_cast<const T *>(d);
+	dst = b.as<const T>();
+	p->uploads.push_back(std::move(b));
 	return MBIK_OK;
 }
 
@@ -45,12 +81,7 @@ int upload_topology(mbik_plan *p) {
 	std::vector<int4> rows(h.sched.size());
 	for (size_t i = 0; i < rows.size(); i++) {
 		// .w: the SCHED_* bits, and above bit 8 the row's longest segment in bone-steps (row_steps)
-		const size_t r0 = i / (size_t)h.K * (size_t)h.K;
-		int nq = 0;
-		for (int l = 0; l < h.K; l++) {
-			const int sg = h.sched[r0 + l].seg;
-			if (sg >= 0) nq = std::max(nq, h.seg_bone_off[sg + 1] - h.seg_bone_off[sg]);
-		}
+		const int nq = mbik::row_max_steps(h, (int)(i / (size_t)h.K));
 		rows[i] = make_int4(h.sched[i].seg, h.sched[i].j, h.sched[i].m, h.sched[i].flags | (nq << 8));
 	}
 	add(rows.data(), rows.size() * sizeof(int4), 4, d.o_sched);
@@ -59,12 +90,11 @@ int upload_topology(mbik_plan *p) {
 	MBIK_TOPO_TABLES(MBIK_ADD)
 #undef MBIK_ADD
 	while (blob.size() % 4) blob.push_back(0);
-	if (p->d_sched) (void)hipFree(p->d_sched);
-	p->d_sched = nullptr;
-	if (hipMalloc(&p->d_sched, blob.size() * 4) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc topology blob");
-	if (hipMemcpy(p->d_sched, blob.data(), blob.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+	p->topo.reset(); // (exactly the blob's size: a smaller one may follow a larger)
+	if (int rc = p->topo.reserve(blob.size() * 4, "hipMalloc topology blob")) return rc;
+	if (hipMemcpy(p->topo.as<void>(), blob.data(), blob.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
 		return fail(MBIK_EHIP, "hipMemcpy topology blob");
-	d.topo_blob = reinterpret_cast<const uint4 *>(p->d_sched);
+	d.topo_blob = p->topo.as<const uint4>();
 	d.topo_words = (int)blob.size();
 	// diagnostics (tools/topo_const.py): the blob's table offsets, for a timing-only build that
 	// compiles one plan's offsets in (solve_block.h MBIK_TOPO_CONST)
@@ -83,9 +113,9 @@ int upload_topology(mbik_plan *p) {
 bool tables_fit_32(const mbik_plan *p) {
 	const mbik::HostPlan &h = p->host;
 	if (p->tab64) return false;
-	const size_t n = (size_t)(h.N + kRowTile - 1) / kRowTile * kRowTile;
-	return (size_t)h.B * 9 * n * sizeof(float) <= kMaxBufBytes && (size_t)h.NC * h.cf_stride() * n * sizeof(float) <= kMaxBufBytes &&
-			(size_t)h.NC * h.cd_stride() * n * sizeof(double) <= kMaxBufBytes;
+	const size_t n = h.padded_n();
+	return h.d_floats(n) * sizeof(float) <= kMaxBufBytes && h.cf_floats(n) * sizeof(float) <= kMaxBufBytes &&
+			h.cd_doubles(n) * sizeof(double) <= kMaxBufBytes;
 }
 // The solve kernel instantiation of a plan's current layout (stabilization x locals placement
 // x waves per SIMD, and for placement 0 the table addressing): k_solve_w1.hip, k_solve_w2.hip,
@@ -101,16 +131,20 @@ mbik::SolveKernel solve_kernel_for(const mbik_plan *p) {
 	return mbik::solve_kernel_w1(h.stabilization_passes > 0, pl, t32, p->dev.prio_mask);
 }
 
+// A classic block's LDS: its spw skeletons' state and one copy of the topology blob.
+static size_t block_lds_bytes(const mbik_plan *p) {
+	return ((size_t)p->host.spw * p->dev.lds_stride + p->dev.topo_words) * sizeof(float);
+}
+
 // Whether a launch of the plan's current layout runs with the helper wave
 // (mbik_solve_kernel_help): asked for, and a layout it serves -- state in LDS, no
 // stabilization, one wave per SIMD, 32-bit tables -- whose block LDS still fits with the ring.
 bool helper_on(const mbik_plan *p) {
 	const mbik::HostPlan &h = p->host;
-	if (p->helper_override != 1) return false;
+	if (p->pins.helper != 1) return false;
 	// (packed levels run row by row there: both waves walk the same rows)
 	if (h.state_hbm != 0 || h.stabilization_passes != 0 || h.waves_per_simd != 1 || h.constraint_mode || !tables_fit_32(p)) return false;
-	const size_t lds = ((size_t)h.spw * p->dev.lds_stride + p->dev.topo_words) * sizeof(float) + kHelpRingBytes;
-	return lds <= 160 * 1024;
+	return block_lds_bytes(p) + kHelpRingBytes <= (size_t)mbik::kLdsBytes;
 }
 
 // The helper wave's handshake deadline: a wait gives up when the awaited counter has not moved
@@ -153,7 +187,7 @@ int blocks_per_cu(void *ctx, int64_t lds_bytes) {
 	int n = 0;
 	const void *k = (const void *)solve_kernel_for(p);
 	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 64, (size_t)lds_bytes) != hipSuccess || n <= 0)
-		return (int)(160 * 1024 / std::max<int64_t>(1, lds_bytes));
+		return (int)(mbik::kLdsBytes / std::max<int64_t>(1, lds_bytes));
 	return n;
 }
 
@@ -161,32 +195,31 @@ int blocks_per_cu(void *ctx, int64_t lds_bytes) {
 // cheap and its state lives in HBM, so the chip's VALU issue (many narrow waves), not one
 // skeleton's chain, bounds it beyond that (C2 / C3 / C5: DESIGN.md §1, profiles/r01_cmode_lanes_sweep.jsonl).
 constexpr int kCmodeLanes = 4;
-// The constraint_mode wave-roles block's LDS for this launch, bounded from the host plan alone
-// (the topology blob's upper bound; cmode_lds_bytes needs the uploaded blob and node state).
-static int64_t cmode_rw_lds_bound(const mbik_plan *p, int64_t nlaunch) {
-	const mbik::HostPlan &h = p->host;
-	const int64_t W = std::max(1, (h.cm_npos + 31) / 32);
-	const int64_t spw = cmode_shape_of(p, nlaunch).spw;
-	return mbik::topology_bytes(h) + (2 * (int64_t)h.B + spw * 4 * W + (int64_t)h.K * 64 * h.cm_maxd + (int64_t)h.K * 4 * 64 + 64) * 4;
+// The constraint_mode wave-roles block's LDS: the topology (topo_bytes), the pre-order tables, the
+// dirty words of its spw skeletons, then per wave the chain stacks and pending cleanings, and the
+// flags.  ensure_schedule bounds it from the host plan alone (topology_bytes: the blob's upper
+// bound); a launch has the uploaded blob's size (cmode_lds_bytes).
+static int64_t cmode_rw_lds(const mbik::HostPlan &h, int64_t topo_bytes, int64_t spw) {
+	return topo_bytes + (2 * (int64_t)h.B + spw * 4 * h.cm_dirty_words() + (int64_t)h.K * 64 * h.cm_maxd + (int64_t)h.K * 4 * 64 + 64) * 4;
 }
 
 // roles_ok false: the classic layout even where wave roles are asked for (their block does not
 // fit the LDS, below).
 static int ensure_schedule_as(mbik_plan *p, int64_t nlaunch, bool roles_ok) {
 	mbik::HostPlan &h = p->host;
-	int lanes = p->lanes_override;
-	if (lanes == 0 && h.constraint_mode && p->cm_lanes > 0) lanes = p->cm_lanes;
-	h.staging = p->staging_override < 0 ? 1 : p->staging_override;
-	h.state_hbm = h.constraint_mode ? 0 : std::max(0, p->locals_override);
-	h.waves_per_simd = (p->waves_override == 2 && !h.constraint_mode && h.stabilization_passes == 0) ? 2 : 1;
+	int lanes = p->pins.lanes;
+	if (lanes == 0 && h.constraint_mode && p->pins.cm_lanes > 0) lanes = p->pins.cm_lanes;
+	h.staging = p->pins.staging < 0 ? 1 : p->pins.staging;
+	h.state_hbm = h.constraint_mode ? 0 : std::max(0, p->pins.locals);
+	h.waves_per_simd = (p->pins.waves == 2 && !h.constraint_mode && h.stabilization_passes == 0) ? 2 : 1;
 	// Wave roles (mbik_plan_set_wave_roles): the whole state in device memory, one wave per role
 	// (K = 2, 4 or 8 waves per block; 8 only at two waves per SIMD), no stabilization, 32-bit tables.
-	h.wave_roles = roles_ok && p->roles_override == 1 && !h.constraint_mode && h.stabilization_passes == 0 && tables_fit_32(p) ? 1 : 0;
+	h.wave_roles = roles_ok && p->pins.roles == 1 && !h.constraint_mode && h.stabilization_passes == 0 && tables_fit_32(p) ? 1 : 0;
 	if (h.wave_roles) {
 		const int cap = 4 * h.waves_per_simd;
 		int roles = std::min(lanes, cap);
 		if (roles == 0) {
-			mbik::build_schedule(h, 0, nlaunch, 0, p->interval_override, nullptr, nullptr, p->cu_count);
+			mbik::build_schedule(h, 0, nlaunch, 0, p->pins.interval, nullptr, nullptr, p->cu_count);
 			roles = std::min(h.K, cap);
 		}
 		// one role is the classic layout with 64 skeletons per wave: no wave roles then
@@ -200,8 +233,8 @@ static int ensure_schedule_as(mbik_plan *p, int64_t nlaunch, bool roles_ok) {
 	}
 	// constraint_mode with wave roles (cmode.h mbik_cmode_kernel_rw): K = 2, 4 or 8 waves per block
 	h.cm_roles = 0;
-	if (roles_ok && h.constraint_mode && p->roles_override == 1 && h.stabilization_passes == 0 && tables_fit_32(p) &&
-			node_area_floats(3 * h.B + 2 * h.NC, (size_t)h.N) * sizeof(float) < (size_t(1) << 32)) {
+	if (roles_ok && h.constraint_mode && p->pins.roles == 1 && h.stabilization_passes == 0 && tables_fit_32(p) &&
+			cmode_node_bytes(h) < (size_t(1) << 32)) {
 		int roles = 1;
 		while (roles < (lanes > 0 ? lanes : kCmodeLanes)) roles <<= 1;
 		roles = std::min(8, roles);
@@ -212,28 +245,27 @@ static int ensure_schedule_as(mbik_plan *p, int64_t nlaunch, bool roles_ok) {
 	}
 	if (h.state_hbm >= 1 && !tables_fit_32(p))
 		return fail(MBIK_EUNSUPPORTED, "state placements 1 and 2 need every setup table < 4 GiB (fewer skeletons per plan)");
-	if (h.state_hbm >= 1 && !p->d_locals) {
+	if (h.state_hbm >= 1 && !p->locals) {
 		// LocTiled: whole tiles of kLocTile skeletons
 		const size_t bytes = (size_t)((h.N + kLocTile - 1) / kLocTile) * kLocTile * h.B * 12 * sizeof(float);
-		if (hipMalloc(&p->d_locals, bytes) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc locals");
-		p->allocs.push_back(p->d_locals);
-		p->device_bytes += (int64_t)bytes;
-		p->dev.Lg = p->d_locals;
+		if (int rc = reserve_counted(p, p->locals, bytes, "hipMalloc locals")) return rc;
+		p->dev.Lg = p->locals.as<float>();
 		p->dev.lg_bytes = (uint32_t)std::min<size_t>(bytes, 0xFFFFFFFFu); // (placement 2 refuses > kMaxBufBytes)
 	}
 	// split-exchange (staging 4 / 5) runs in the 32-bit-table two-wave builds; the 64-bit-index
 	// two-wave build solves those segments alone (4 -> 0) or staged (5 -> 2)
 	if (h.waves_per_simd == 2 && !tables_fit_32(p) && h.staging >= 4) h.staging = h.staging == 4 ? 0 : 2;
-	mbik::build_schedule(h, lanes, nlaunch, p->spw_override, p->interval_override, blocks_per_cu, p, p->cu_count);
+	mbik::build_schedule(h, lanes, nlaunch, p->pins.spw, p->pins.interval, blocks_per_cu, p, p->cu_count);
 	if (lanes == 0 && h.constraint_mode && h.K > kCmodeLanes && !h.cm_roles)
-		mbik::build_schedule(h, kCmodeLanes, nlaunch, p->spw_override, p->interval_override, blocks_per_cu, p, p->cu_count);
+		mbik::build_schedule(h, kCmodeLanes, nlaunch, p->pins.spw, p->pins.interval, blocks_per_cu, p, p->cu_count);
 	// A wave-roles block holds the topology, the non-finite flags and, with cooperative rows, the
 	// block's targets and the effector-global exchange (the root segment's row alone takes a slot
 	// per pin); constraint_mode's holds per-wave chain stacks of the deepest pose chain.  Where that
 	// exceeds the LDS the plan falls back to the classic layout, as it does for stabilization or
 	// 64-bit tables: a pinned mbik_plan_set_wave_roles(1) still solves, and the autotune times the
 	// classic layout for such a candidate instead of failing on it.
-	if (roles_ok && ((h.wave_roles && h.lds_block_bytes > 160 * 1024) || (h.cm_roles && cmode_rw_lds_bound(p, nlaunch) > 160 * 1024)))
+	if (roles_ok && ((h.wave_roles && h.lds_block_bytes > mbik::kLdsBytes) ||
+							(h.cm_roles && cmode_rw_lds(h, mbik::topology_bytes(h), cmode_shape_of(p, nlaunch).spw) > mbik::kLdsBytes)))
 		return ensure_schedule_as(p, nlaunch, false);
 	if (h.state_hbm == 2) {
 		// the whole state in device memory: one skeleton's LDS layout per skeleton (the locals
@@ -243,40 +275,16 @@ static int ensure_schedule_as(mbik_plan *p, int64_t nlaunch, bool roles_ok) {
 		const size_t gneed = (size_t)((h.N + kLocTile - 1) / kLocTile) * kLocTile * (size_t)std::max(1, h.n_gck) * 12;
 		if (need * sizeof(float) > kMaxBufBytes || p->dev.lg_bytes > kMaxBufBytes || gneed * sizeof(float) > kMaxBufBytes)
 			return fail(MBIK_EUNSUPPORTED, "solve state in device memory needs < 4 GiB per area (fewer skeletons per plan)");
-		if (gneed > p->d_gtile_floats) {
-			void *a = nullptr;
-			if (hipMalloc(&a, gneed * sizeof(float)) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc checkpoint globals");
-			if (p->d_gtile) {
-				(void)hipFree(p->d_gtile);
-				p->allocs.erase(std::remove(p->allocs.begin(), p->allocs.end(), (void *)p->d_gtile), p->allocs.end());
-				p->device_bytes -= (int64_t)(p->d_gtile_floats * sizeof(float));
-			}
-			p->d_gtile = static_cast<float *>(a);
-			p->d_gtile_floats = gneed;
-			p->allocs.push_back(a);
-			p->device_bytes += (int64_t)(gneed * sizeof(float));
-		}
-		p->dev.Gg = p->d_gtile;
-		p->dev.gg_bytes = (uint32_t)(p->d_gtile_floats * sizeof(float));
-		if (need > p->d_state_floats) {
-			void *a = nullptr;
-			if (hipMalloc(&a, need * sizeof(float)) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc state");
-			if (p->d_state) {
-				(void)hipFree(p->d_state);
-				p->allocs.erase(std::remove(p->allocs.begin(), p->allocs.end(), (void *)p->d_state), p->allocs.end());
-				p->device_bytes -= (int64_t)(p->d_state_floats * sizeof(float));
-			}
-			p->d_state = static_cast<float *>(a);
-			p->d_state_floats = need;
-			p->allocs.push_back(a);
-			p->device_bytes += (int64_t)(need * sizeof(float));
-		}
-		p->dev.Sg = p->d_state;
-		p->dev.sg_bytes = (uint32_t)(p->d_state_floats * sizeof(float));
+		if (int rc = reserve_counted(p, p->gtile, gneed * sizeof(float), "hipMalloc checkpoint globals")) return rc;
+		p->dev.Gg = p->gtile.as<float>();
+		p->dev.gg_bytes = (uint32_t)p->gtile.bytes();
+		if (int rc = reserve_counted(p, p->state, need * sizeof(float), "hipMalloc state")) return rc;
+		p->dev.Sg = p->state.as<float>();
+		p->dev.sg_bytes = (uint32_t)p->state.bytes();
 		p->dev.state_stride = stride;
 	}
 	if (p->sched_K == h.K && p->sched_c == h.g_interval && p->sched_staging == h.staging &&
-			p->sched_locals == h.state_hbm && p->sched_roles == (h.wave_roles | h.cm_roles << 1) && p->d_sched) {
+			p->sched_locals == h.state_hbm && p->sched_roles == (h.wave_roles | h.cm_roles << 1) && p->topo) {
 		p->dev.spw = h.spw;
 		return MBIK_OK;
 	}
@@ -311,26 +319,23 @@ static size_t cmode_wave_words(const mbik_plan *p, int spw) {
 }
 // constraint_mode launch shape: spw skeletons per wave (cm_spw_div halves 64 / K that many
 // times), and as many waves per block (<= kCmodeMaxWaves) as share the block's LDS within
-// 160 KiB and leave the launch with at least one block per CU.
+// kLdsBytes and leave the launch with at least one block per CU.
 CmShape cmode_shape_of(const mbik_plan *p, int64_t count) {
 	const mbik::HostPlan &h = p->host;
 	if (h.cm_roles) // wave roles: a block is K waves x spw skeletons (64, halved cm_spw_div times)
-		return CmShape{p->spw_override > 0 ? std::min(64, p->spw_override) : std::max(1, 64 >> std::max(0, p->cm_spw_div)), 1};
+		return CmShape{p->pins.spw > 0 ? std::min(64, p->pins.spw) : std::max(1, 64 >> std::max(0, p->pins.cm_spw_div)), 1};
 	const int full = 64 >> h.log2K;
-	const int spw = p->spw_override > 0 ? std::min(full, p->spw_override) : std::max(1, full >> std::max(0, p->cm_spw_div));
+	const int spw = p->pins.spw > 0 ? std::min(full, p->pins.spw) : std::max(1, full >> std::max(0, p->pins.cm_spw_div));
 	int wpb = kCmodeMaxWaves;
 	const size_t fixed = (size_t)p->dev.topo_words + 2 * (size_t)h.B;
-	while (wpb > 1 && ((fixed + (size_t)wpb * cmode_wave_words(p, spw)) * sizeof(float) > 160 * 1024 ||
+	while (wpb > 1 && ((fixed + (size_t)wpb * cmode_wave_words(p, spw)) * sizeof(float) > (size_t)mbik::kLdsBytes ||
 							  (size_t)(count + (int64_t)wpb * spw - 1) / ((size_t)wpb * spw) < (size_t)p->cu_count))
 		wpb >>= 1;
 	return CmShape{spw, wpb};
 }
 size_t cmode_lds_bytes(const mbik_plan *p, CmShape sh) {
 	const mbik::HostPlan &h = p->host;
-	if (h.cm_roles) // topology, pre-order tables, dirty words, per wave the chain stacks, pending cleanings, flags
-		return ((size_t)p->dev.topo_words + 2 * (size_t)h.B + (size_t)sh.spw * 4 * p->cm.W + (size_t)h.K * 64 * p->cm.maxd +
-					   (size_t)h.K * 4 * 64 + 64) *
-				sizeof(float);
+	if (h.cm_roles) return (size_t)cmode_rw_lds(h, (int64_t)p->dev.topo_words * 4, sh.spw);
 	return ((size_t)p->dev.topo_words + 2 * (size_t)h.B + (size_t)sh.wpb * cmode_wave_words(p, sh.spw)) * sizeof(float);
 }
 void cmode_shape(mbik_plan *p, int count) {
@@ -350,9 +355,11 @@ int cmode_reset(mbik_plan *p, int first, int count, const float *setup_pose, hip
 
 // Plan files keep constraint_mode's node caches in the plain [slot][12][N] order (format 1's);
 // the device holds them skeleton-tiled (node_at).
-size_t cmode_file_node_bytes(const mbik::HostPlan &h) { return (size_t)(3 * h.B + 2 * h.NC) * 12 * (size_t)h.N * sizeof(float); }
+size_t cmode_file_node_bytes(const mbik::HostPlan &h) { return (size_t)h.cm_slots() * 12 * (size_t)h.N * sizeof(float); }
+size_t cmode_node_bytes(const mbik::HostPlan &h) { return node_area_floats(h.cm_slots(), (size_t)h.N) * sizeof(float); }
+size_t cmode_dirty_bytes(const mbik::HostPlan &h) { return 4 * (size_t)h.cm_dirty_words() * (size_t)h.N * sizeof(uint32_t); }
 std::vector<float> cmode_nodes_tiled(const mbik::HostPlan &h, const float *plain) {
-	const int slots = 3 * h.B + 2 * h.NC;
+	const int slots = h.cm_slots();
 	const size_t N = (size_t)h.N;
 	std::vector<float> t(node_area_floats(slots, N), 0.0f);
 	for (int k = 0; k < slots; k++)
@@ -361,7 +368,7 @@ std::vector<float> cmode_nodes_tiled(const mbik::HostPlan &h, const float *plain
 	return t;
 }
 void cmode_nodes_plain(const mbik::HostPlan &h, const float *tiled, float *plain) {
-	const int slots = 3 * h.B + 2 * h.NC;
+	const int slots = h.cm_slots();
 	const size_t N = (size_t)h.N;
 	for (int k = 0; k < slots; k++)
 		for (int f = 0; f < 12; f++)
@@ -373,28 +380,24 @@ void cmode_nodes_plain(const mbik::HostPlan &h, const float *tiled, float *plain
 int cmode_create(mbik_plan *p, const float *setup_pose, const void *saved) {
 	const mbik::HostPlan &h = p->host;
 	CmodeState &c = p->cm;
-	c.W = std::max(1, (h.cm_npos + 31) / 32);
+	c.W = h.cm_dirty_words();
 	c.maxd = h.cm_maxd;
 	int rc = upload(p, h.cm_pre, c.pre);
 	rc = rc ? rc : upload(p, h.cm_sub, c.sub);
 	if (rc) return rc;
 	const size_t N = (size_t)h.N;
-	const size_t node_bytes = node_area_floats(3 * h.B + 2 * h.NC, N) * sizeof(float);
-	const size_t dirty_bytes = 4 * (size_t)c.W * N * sizeof(uint32_t);
-	void *a = nullptr, *d = nullptr, *sp = nullptr;
-	if (hipMalloc(&a, std::max<size_t>(node_bytes, 4)) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc constraint_mode node caches");
-	p->allocs.push_back(a);
-	if (hipMalloc(&d, std::max<size_t>(dirty_bytes, 4)) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc constraint_mode dirty bits");
-	p->allocs.push_back(d);
+	const size_t node_bytes = cmode_node_bytes(h), dirty_bytes = cmode_dirty_bytes(h);
+	if ((rc = p->cm_node.reserve(std::max<size_t>(node_bytes, 4), "hipMalloc constraint_mode node caches")) != MBIK_OK) return rc;
+	if ((rc = p->cm_dirty.reserve(std::max<size_t>(dirty_bytes, 4), "hipMalloc constraint_mode dirty bits")) != MBIK_OK) return rc;
 	p->device_bytes += (int64_t)(node_bytes + dirty_bytes);
-	c.node = static_cast<float *>(a);
-	c.dirty = static_cast<uint32_t *>(d);
+	c.node = p->cm_node.as<float>();
+	c.dirty = p->cm_dirty.as<uint32_t>();
 	if (N == 0) return MBIK_OK;
 	if (saved) { // mbik_plan_load: the saved frame-to-frame node caches ([slot][12][N] in the file)
 		const char *sv = static_cast<const char *>(saved);
 		const std::vector<float> tiled = cmode_nodes_tiled(h, reinterpret_cast<const float *>(sv));
-		if (hipMemcpy(a, tiled.data(), node_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-				hipMemcpy(d, sv + cmode_file_node_bytes(h), dirty_bytes, hipMemcpyHostToDevice) != hipSuccess)
+		if (hipMemcpy(c.node, tiled.data(), node_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+				hipMemcpy(c.dirty, sv + cmode_file_node_bytes(h), dirty_bytes, hipMemcpyHostToDevice) != hipSuccess)
 			return fail(MBIK_EHIP, "hipMemcpy constraint_mode state");
 		return MBIK_OK;
 	}
@@ -404,53 +407,43 @@ int cmode_create(mbik_plan *p, const float *setup_pose, const void *saved) {
 		return rc;
 	}
 	const size_t pose_bytes = N * h.B * 10 * sizeof(float);
-	if (hipMalloc(&sp, pose_bytes) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc setup pose");
-	rc = hipMemcpy(sp, setup_pose, pose_bytes, hipMemcpyHostToDevice) == hipSuccess ? MBIK_OK : fail(MBIK_EHIP, "hipMemcpy setup pose");
-	if (rc == 0) rc = cmode_reset(p, 0, (int)N, static_cast<const float *>(sp), nullptr);
+	DevBuf sp;
+	if ((rc = sp.reserve(pose_bytes, "hipMalloc setup pose")) != MBIK_OK) return rc;
+	rc = hipMemcpy(sp.as<void>(), setup_pose, pose_bytes, hipMemcpyHostToDevice) == hipSuccess ? MBIK_OK : fail(MBIK_EHIP, "hipMemcpy setup pose");
+	if (rc == 0) rc = cmode_reset(p, 0, (int)N, sp.as<const float>(), nullptr);
 	if (rc == 0 && hipDeviceSynchronize() != hipSuccess) rc = fail(MBIK_EHIP, "constraint_mode reset");
-	(void)hipFree(sp);
 	return rc;
 }
 
 // The skeleton-tiled copies of the plan's D / CF / CD (DevPlan::row_at) for launches with the
 // whole state in device memory, (re)built on the launch stream when the tables changed.
 int ensure_tiled_rows(mbik_plan *p, hipStream_t stream) {
-	if (p->tiled_version == p->tables_version && p->d_Dt) return MBIK_OK;
+	if (p->tiled_version == p->tables_version && p->Dt) return MBIK_OK;
 	const mbik::HostPlan &h = p->host;
-	const int Npad = (h.N + kRowTile - 1) / kRowTile * kRowTile;
-	const size_t nD = (size_t)h.B * 9 * Npad, nCF = (size_t)h.NC * h.cf_stride() * Npad, nCD = (size_t)h.NC * h.cd_stride() * Npad;
-	if (!p->d_Dt) {
-		void *a = nullptr, *b = nullptr, *c = nullptr;
-		if (hipMalloc(&a, std::max<size_t>(nD, 1) * sizeof(float)) != hipSuccess ||
-				hipMalloc(&b, std::max<size_t>(nCF, 1) * sizeof(float)) != hipSuccess ||
-				hipMalloc(&c, std::max<size_t>(nCD, 1) * sizeof(double)) != hipSuccess) {
-			if (a) (void)hipFree(a);
-			if (b) (void)hipFree(b);
-			if (c) (void)hipFree(c);
-			return fail(MBIK_ENOMEM, "hipMalloc tiled setup tables");
-		}
+	const int Npad = (int)h.padded_n();
+	const size_t nD = h.d_floats(Npad), nCF = h.cf_floats(Npad), nCD = h.cd_doubles(Npad);
+	if (!p->Dt) {
+		DevBuf a, b, c;
+		const size_t bD = std::max<size_t>(nD, 1) * sizeof(float), bCF = std::max<size_t>(nCF, 1) * sizeof(float),
+					 bCD = std::max<size_t>(nCD, 1) * sizeof(double);
+		if (a.reserve(bD, "hipMalloc tiled setup tables") || b.reserve(bCF, "hipMalloc tiled setup tables") ||
+				c.reserve(bCD, "hipMalloc tiled setup tables"))
+			return MBIK_ENOMEM;
 		// padding skeletons read zeros
-		if (hipMemsetAsync(a, 0, std::max<size_t>(nD, 1) * sizeof(float), stream) != hipSuccess ||
-				hipMemsetAsync(b, 0, std::max<size_t>(nCF, 1) * sizeof(float), stream) != hipSuccess ||
-				hipMemsetAsync(c, 0, std::max<size_t>(nCD, 1) * sizeof(double), stream) != hipSuccess) {
-			(void)hipStreamSynchronize(stream);
-			(void)hipFree(a);
-			(void)hipFree(b);
-			(void)hipFree(c);
+		if (hipMemsetAsync(a.as<void>(), 0, bD, stream) != hipSuccess || hipMemsetAsync(b.as<void>(), 0, bCF, stream) != hipSuccess ||
+				hipMemsetAsync(c.as<void>(), 0, bCD, stream) != hipSuccess) {
+			(void)hipStreamSynchronize(stream); // (the buffers are freed on return)
 			return fail(MBIK_EHIP, "hipMemsetAsync tiled setup tables");
 		}
-		p->d_Dt = static_cast<float *>(a);
-		p->d_CFt = static_cast<float *>(b);
-		p->d_CDt = static_cast<double *>(c);
-		p->allocs.push_back(a);
-		p->allocs.push_back(b);
-		p->allocs.push_back(c);
+		p->Dt = std::move(a);
+		p->CFt = std::move(b);
+		p->CDt = std::move(c);
 		p->device_bytes += (int64_t)((nD + nCF) * sizeof(float) + nCD * sizeof(double));
 	}
 	hipError_t e = hipSuccess;
-	if (nD && e == hipSuccess) e = mbik::launch_tile_rows(stream, p->dev.D, p->d_Dt, h.B, 9, h.N, Npad);
-	if (nCF && e == hipSuccess) e = mbik::launch_tile_rows(stream, p->dev.CF, p->d_CFt, h.NC, h.cf_stride(), h.N, Npad);
-	if (nCD && e == hipSuccess) e = mbik::launch_tile_rows(stream, p->dev.CD, p->d_CDt, h.NC, h.cd_stride(), h.N, Npad);
+	if (nD && e == hipSuccess) e = mbik::launch_tile_rows(stream, p->dev.D, p->Dt.as<float>(), h.B, 9, h.N, Npad);
+	if (nCF && e == hipSuccess) e = mbik::launch_tile_rows(stream, p->dev.CF, p->CFt.as<float>(), h.NC, h.cf_stride(), h.N, Npad);
+	if (nCD && e == hipSuccess) e = mbik::launch_tile_rows(stream, p->dev.CD, p->CDt.as<double>(), h.NC, h.cd_stride(), h.N, Npad);
 	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("tile launch failed: ") + hipGetErrorString(e));
 	// A launch on another stream must not read the copy before the tiling has run: record its
 	// completion; launch() makes other streams wait on it until it has completed.
@@ -495,9 +488,9 @@ int launch(mbik_plan *p, int first, int count, const float *pose_in, const float
 	if (h.constraint_mode) {
 		cmode_shape(p, count);
 		const size_t clds = cmode_lds_bytes(p, CmShape{p->cm.spw, p->cm.wpb});
-		if (clds > 160 * 1024) return fail(MBIK_EUNSUPPORTED, "skeleton too large for the constraint_mode LDS layout");
+		if (clds > (size_t)mbik::kLdsBytes) return fail(MBIK_EUNSUPPORTED, "skeleton too large for the constraint_mode LDS layout");
 		// node caches below 4 GiB: buffer-resource addressing (cmode.h, NB32)
-		const bool nb32 = node_area_floats(3 * h.B + 2 * h.NC, (size_t)h.N) * sizeof(float) < (size_t(1) << 32) && tables_fit_32(p);
+		const bool nb32 = cmode_node_bytes(h) < (size_t(1) << 32) && tables_fit_32(p);
 		mbik::CmodeKernel ck = mbik::cmode_kernel(h.stabilization_passes > 0, nb32, h.has_chain);
 		const int per_block = p->cm.spw * p->cm.wpb;
 		unsigned threads = 64 * p->cm.wpb;
@@ -513,9 +506,9 @@ int launch(mbik_plan *p, int first, int count, const float *pose_in, const float
 		if (e != hipSuccess) return fail(MBIK_EHIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
 		return MBIK_OK;
 	}
-	size_t lds = ((size_t)h.spw * p->dev.lds_stride + p->dev.topo_words) * sizeof(float);
+	size_t lds = block_lds_bytes(p);
 	if constexpr (kAblate & ABL_SOALDS) lds += ((size_t)p->dev.B * 9 + p->dev.NC * p->dev.cf_stride + 2 * p->dev.NC * p->dev.cd_stride + 2) * sizeof(float);
-	if (lds > 160 * 1024) return fail(MBIK_EUNSUPPORTED, "skeleton too large for LDS at this lane count");
+	if (lds > (size_t)mbik::kLdsBytes) return fail(MBIK_EUNSUPPORTED, "skeleton too large for LDS at this lane count");
 	unsigned blocks = (unsigned)((count + h.spw - 1) / h.spw);
 	auto kern = solve_kernel_for(p);
 	unsigned threads = 64;
@@ -523,8 +516,8 @@ int launch(mbik_plan *p, int first, int count, const float *pose_in, const float
 		threads = 64u * (unsigned)h.K; // a wave per role
 		// non-finite flags; with cooperative rows the targets, the effector-global exchange and the
 		// groups' parent-side records
-		lds += 64 * sizeof(int) + (h.rw_xslots ? ((size_t)h.P + h.rw_xslots) * 12 * 64 * sizeof(float) + mbik::rw_record_bytes(h) : 0);
-		if (lds > 160 * 1024) return fail(MBIK_EUNSUPPORTED, "wave roles: a row's effector-global exchange exceeds the LDS");
+		lds += (size_t)mbik::rw_extra_lds_bytes(h);
+		if (lds > (size_t)mbik::kLdsBytes) return fail(MBIK_EUNSUPPORTED, "wave roles: a row's effector-global exchange exceeds the LDS");
 		// the cooperative groups' record handshake has a deadline and reports through the plan's
 		// timeout flag, as the helper wave's does (rw_wait)
 		if (h.rw_xslots && (rc = ensure_help_flag(p)) != MBIK_OK) return rc;
@@ -544,10 +537,10 @@ int launch(mbik_plan *p, int first, int count, const float *pose_in, const float
 	if (h.state_hbm == 2) {
 		if ((rc = ensure_tiled_rows(p, stream)) != MBIK_OK) return rc;
 		if ((rc = wait_tiled_rows(p, stream)) != MBIK_OK) return rc;
-		d.D = p->d_Dt;
-		d.CF = p->d_CFt;
-		d.CD = p->d_CDt;
-		d.row_n = (h.N + kRowTile - 1) / kRowTile * kRowTile;
+		d.D = p->Dt.as<float>();
+		d.CF = p->CFt.as<float>();
+		d.CD = p->CDt.as<double>();
+		d.row_n = (int)h.padded_n();
 	}
 	hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, stream, d, first, count, pose_in, targets, pose_out,
 			iterations, seg_lo, seg_hi);
@@ -570,6 +563,12 @@ int read_options(const mbik_plan_options *opts, int &libm) {
 }
 
 } // namespace mbik_host
+
+mbik_plan::~mbik_plan() {
+	DeviceGuard guard(device);
+	if (tile_ev) (void)hipEventDestroy(tile_ev);
+	if (help_flag) (void)hipHostFree(help_flag);
+}
 
 extern "C" {
 
@@ -604,9 +603,7 @@ int32_t mbik_plan_create_opts(const mbik_skeleton_desc *desc, const mbik_config 
 	int libm = 0;
 	if (read_options(opts, libm)) return MBIK_EINVAL;
 	*out_plan = nullptr;
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MBIK_ENODEV, "no HIP device visible");
-	if (device < 0 || device >= ndev) return fail(MBIK_EINVAL, "device index out of range");
+	if (int rc = check_device(device)) return rc;
 	std::unique_ptr<mbik_plan> p(new mbik_plan());
 	p->device = device;
 	if (desc->bone_count < 0 || desc->pin_count < 0 || desc->constraint_count < 0 || config->bone_damp_count < 0)
@@ -648,11 +645,7 @@ int finish_plan(mbik_plan *p, const float *setup_pose, const void *cm_state) {
 			if (p->host.eff_path_off[e + 1] - p->host.eff_path_off[e] > 4096) return fail(MBIK_EUNSUPPORTED, "skeleton too deep");
 		}
 	DeviceGuard guard(device);
-	{
-		int cus = 0;
-		if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
-			p->cu_count = cus;
-	}
+	p->cu_count = cu_count_of(device);
 	mbik::HostPlan &h = p->host;
 	DevPlan &d = p->dev;
 	d.B = h.B; d.P = h.P; d.NS = h.NS; d.NC = h.NC; d.max_cones = h.max_cones; d.N = h.N;
@@ -677,20 +670,9 @@ int finish_plan(mbik_plan *p, const float *setup_pose, const void *cm_state) {
 	rc = rc ? rc : upload(p, h.D, d.D);
 	rc = rc ? rc : upload(p, h.CF, d.CF);
 	rc = rc ? rc : upload(p, h.CD, d.CD);
-	if (rc) {
-		for (void *a : p->allocs) (void)hipFree(a);
-		p->allocs.clear();
-		return rc;
-	}
-	rc = ensure_schedule(p, n_skeletons);
+	rc = rc ? rc : ensure_schedule(p, n_skeletons);
 	if (rc == 0 && h.constraint_mode) rc = cmode_create(p, setup_pose, cm_state);
-	if (rc) {
-		for (void *a : p->allocs) (void)hipFree(a);
-		p->allocs.clear();
-		if (p->d_sched) (void)hipFree(p->d_sched);
-		p->d_sched = nullptr;
-		return rc;
-	}
+	if (rc) return rc; // (the caller deletes the plan, which frees what it took)
 	// Algorithmic flops: per bone-step 50 H + 14 H [translate] + 72 E_seg
 	// + 465, plus 770 + 140 C - 60 for a constrained bone with C cones; x iterations.
 	double f = 0;
@@ -719,7 +701,7 @@ int finish_plan(mbik_plan *p, const float *setup_pose, const void *cm_state) {
 	for (int c = 0; c < h.NC; c++) cons += 16.0 * 3 + 4.0 + 52.0 * h.cons_ncones[c];
 	p->alg_bytes = (double)h.B * (40 + 16 + 4 + 40) + (double)h.P * (48 + 16) + cons;
 	if (h.constraint_mode) // the persistent node caches, read and written once per frame
-		p->alg_bytes += 2.0 * ((double)(3 * h.B + 2 * h.NC) * 12 * 4 + 4.0 * p->cm.W * 4);
+		p->alg_bytes += 2.0 * ((double)h.cm_slots() * 12 * 4 + 4.0 * p->cm.W * 4);
 	h.D.clear(); h.D.shrink_to_fit();
 	h.CF.clear(); h.CF.shrink_to_fit();
 	h.CD.clear(); h.CD.shrink_to_fit();
@@ -729,18 +711,7 @@ int finish_plan(mbik_plan *p, const float *setup_pose, const void *cm_state) {
 
 extern "C" {
 
-void mbik_plan_destroy(mbik_plan *p) {
-	if (!p) return;
-	DeviceGuard guard(p->device);
-	for (void *a : p->allocs) (void)hipFree(a);
-	if (p->d_sched) (void)hipFree(p->d_sched);
-	if (p->d_in) (void)hipFree(p->d_in);
-	if (p->d_tg) (void)hipFree(p->d_tg);
-	if (p->d_out) (void)hipFree(p->d_out);
-	if (p->tile_ev) (void)hipEventDestroy(p->tile_ev);
-	if (p->help_flag) (void)hipHostFree(p->help_flag);
-	delete p;
-}
+void mbik_plan_destroy(mbik_plan *p) { delete p; }
 
 int32_t mbik_plan_get_info(const mbik_plan *p, mbik_plan_info *o) {
 	if (!p || !o) return fail(MBIK_EINVAL, "null argument");
@@ -779,7 +750,7 @@ int32_t mbik_plan_get_info(const mbik_plan *p, mbik_plan_info *o) {
 int32_t mbik_plan_set_launch(mbik_plan *p, int32_t lanes) {
 	if (!p) return fail(MBIK_EINVAL, "null plan");
 	if (lanes < 0 || lanes > 64 || (lanes & (lanes - 1))) return fail(MBIK_EINVAL, "lanes_per_skeleton must be 0 or a power of two <= 64");
-	p->lanes_override = lanes;
+	p->pins.lanes = lanes;
 	p->sched_K = -1;
 	return MBIK_OK;
 }
@@ -789,9 +760,9 @@ int32_t mbik_plan_set_layout(mbik_plan *p, int32_t lanes, int32_t skeletons_per_
 	if (lanes < 0 || lanes > 64 || (lanes & (lanes - 1))) return fail(MBIK_EINVAL, "lanes_per_skeleton must be 0 or a power of two <= 64");
 	if (skeletons_per_block < 0 || skeletons_per_block > 64) return fail(MBIK_EINVAL, "skeletons_per_block must be in [0, 64]");
 	if (global_checkpoint_interval < 0) return fail(MBIK_EINVAL, "global_checkpoint_interval must be >= 0");
-	p->lanes_override = lanes;
-	p->spw_override = skeletons_per_block;
-	p->interval_override = global_checkpoint_interval;
+	p->pins.lanes = lanes;
+	p->pins.spw = skeletons_per_block;
+	p->pins.interval = global_checkpoint_interval;
 	p->sched_K = -1;
 	return MBIK_OK;
 }
@@ -799,7 +770,7 @@ int32_t mbik_plan_set_layout(mbik_plan *p, int32_t lanes, int32_t skeletons_per_
 int32_t mbik_plan_set_waves_per_simd(mbik_plan *p, int32_t waves) {
 	if (!p) return fail(MBIK_EINVAL, "null plan");
 	if (waves != -1 && waves != 1 && waves != 2) return fail(MBIK_EINVAL, "waves_per_simd must be -1 (automatic), 1 or 2");
-	p->waves_override = waves;
+	p->pins.waves = waves;
 	p->sched_K = -1;
 	return MBIK_OK;
 }
@@ -807,14 +778,14 @@ int32_t mbik_plan_set_waves_per_simd(mbik_plan *p, int32_t waves) {
 int32_t mbik_plan_set_helper_wave(mbik_plan *p, int32_t helper) {
 	if (!p) return fail(MBIK_EINVAL, "null plan");
 	if (helper < -1 || helper > 1) return fail(MBIK_EINVAL, "helper wave must be -1 (automatic), 0 (off) or 1 (on)");
-	p->helper_override = helper;
+	p->pins.helper = helper;
 	return MBIK_OK;
 }
 
 int32_t mbik_plan_set_wave_roles(mbik_plan *p, int32_t roles) {
 	if (!p) return fail(MBIK_EINVAL, "null plan");
 	if (roles < -1 || roles > 1) return fail(MBIK_EINVAL, "wave roles must be -1 (automatic), 0 (off) or 1 (on)");
-	p->roles_override = roles;
+	p->pins.roles = roles;
 	p->sched_K = -1;
 	return MBIK_OK;
 }
@@ -831,7 +802,7 @@ int32_t mbik_plan_set_locals_placement(mbik_plan *p, int32_t placement) {
 	if (!p) return fail(MBIK_EINVAL, "null plan");
 	if (placement < -1 || placement > 2)
 		return fail(MBIK_EINVAL, "placement must be -1 (automatic), 0 (LDS), 1 (locals in device memory) or 2 (all state)");
-	p->locals_override = placement;
+	p->pins.locals = placement;
 	p->sched_K = -1;
 	return MBIK_OK;
 }
@@ -839,7 +810,7 @@ int32_t mbik_plan_set_locals_placement(mbik_plan *p, int32_t placement) {
 int32_t mbik_plan_set_heading_staging(mbik_plan *p, int32_t staging) {
 	if (!p) return fail(MBIK_EINVAL, "null plan");
 	if (staging < -1 || staging > 5) return fail(MBIK_EINVAL, "staging must be -1 (automatic), 0, 1, 2, 3, 4 or 5");
-	p->staging_override = staging;
+	p->pins.staging = staging;
 	p->sched_K = -1;
 	return MBIK_OK;
 }
@@ -876,16 +847,16 @@ int32_t mbik_plan_rebuild_setup(mbik_plan *p, int32_t first, int32_t count, cons
 	const mbik::SetupView &v = p->dsetup;
 	const size_t stride = (mbik::setup_scratch_bytes(v.B, v.NC, v.max_cones_in) + 255) & ~size_t(255);
 	const int threads = std::min(count, 8192);
-	void *scratch = nullptr;
-	if (hipMalloc(&scratch, stride * (size_t)threads) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc setup scratch");
+	DevBuf scratch;
+	if (int rc = scratch.reserve(stride * (size_t)threads, "hipMalloc setup scratch")) return rc;
 	hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
 	const DevPlan &d = p->dev;
-	hipError_t e = mbik::launch_setup(st, threads, v, first, count, setup_pose, cones, twist, static_cast<char *>(scratch), stride,
+	hipError_t e = mbik::launch_setup(st, threads, v, first, count, setup_pose, cones, twist, scratch.as<char>(), stride,
 			const_cast<float *>(d.D), const_cast<float *>(d.CF), const_cast<double *>(d.CD));
 	// the scratch is freed after the kernel; a fault while it runs surfaces at this sync and
 	// must not be reported as success (the D/CF/CD tables may be partly written)
 	hipError_t es = hipStreamSynchronize(st);
-	(void)hipFree(scratch);
+	scratch.reset();
 	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("setup launch: ") + hipGetErrorString(e));
 	if (es != hipSuccess) return fail(MBIK_EHIP, std::string("setup kernel: ") + hipGetErrorString(es));
 	p->tables_version++;
@@ -899,11 +870,11 @@ int32_t mbik_plan_setup_tables(const mbik_plan *p, float *D, float *CF, double *
 	const mbik::HostPlan &h = p->host;
 	DeviceGuard guard(p->device);
 	const size_t N = (size_t)h.N;
-	if (D && hipMemcpy(D, p->dev.D, (size_t)h.B * 9 * N * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+	if (D && hipMemcpy(D, p->dev.D, h.d_floats(N) * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
 		return fail(MBIK_EHIP, "hipMemcpy D");
-	if (CF && h.NC && hipMemcpy(CF, p->dev.CF, (size_t)h.NC * h.cf_stride() * N * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+	if (CF && h.NC && hipMemcpy(CF, p->dev.CF, h.cf_floats(N) * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
 		return fail(MBIK_EHIP, "hipMemcpy CF");
-	if (CD && h.NC && hipMemcpy(CD, p->dev.CD, (size_t)h.NC * h.cd_stride() * N * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+	if (CD && h.NC && hipMemcpy(CD, p->dev.CD, h.cd_doubles(N) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
 		return fail(MBIK_EHIP, "hipMemcpy CD");
 	return MBIK_OK;
 }
@@ -971,22 +942,14 @@ int32_t mbik_group_create(mbik_plan *const *plans, int32_t n_plans, mbik_group *
 	g->plans.assign(plans, plans + n_plans);
 	g->device = plans[0]->device;
 	DeviceGuard guard(g->device);
-	if (hipMalloc(&g->d_plans, sizeof(DevPlan) * n_plans) != hipSuccess ||
-			hipMalloc(&g->d_entries, sizeof(GroupEntry) * n_plans) != hipSuccess) {
-		if (g->d_plans) (void)hipFree(g->d_plans);
-		return fail(MBIK_ENOMEM, "hipMalloc group tables");
-	}
+	if (g->d_plans.reserve(sizeof(DevPlan) * n_plans, "hipMalloc group tables") ||
+			g->d_entries.reserve(sizeof(GroupEntry) * n_plans, "hipMalloc group tables"))
+		return MBIK_ENOMEM;
 	*out_group = g.release();
 	return MBIK_OK;
 }
 
-void mbik_group_destroy(mbik_group *g) {
-	if (!g) return;
-	DeviceGuard guard(g->device);
-	if (g->d_plans) (void)hipFree(g->d_plans);
-	if (g->d_entries) (void)hipFree(g->d_entries);
-	delete g;
-}
+void mbik_group_destroy(mbik_group *g) { delete g; }
 
 int32_t mbik_group_solve(mbik_group *g, const int32_t *first, const int32_t *count, const float *const *pose_in,
 		const float *const *targets, float *const *pose_out, void *hip_stream) {
@@ -1007,14 +970,7 @@ int32_t mbik_group_solve(mbik_group *g, const int32_t *first, const int32_t *cou
 	for (int i = 0; i < n; i++) {
 		const mbik::HostPlan &h = g->plans[i]->host;
 		double steps = 0;
-		for (int r = 0; r < h.nrows; r++) {
-			int m = 0;
-			for (int l = 0; l < h.K; l++) {
-				const int sg = h.sched[(size_t)r * h.K + l].seg;
-				if (sg >= 0) m = std::max(m, h.seg_bone_off[sg + 1] - h.seg_bone_off[sg]);
-			}
-			steps += m;
-		}
+		for (int r = 0; r < h.nrows; r++) steps += mbik::row_max_steps(h, r);
 		order.push_back({-(double)h.iterations * steps, i});
 	}
 	std::stable_sort(order.begin(), order.end());
@@ -1037,8 +993,8 @@ int32_t mbik_group_solve(mbik_group *g, const int32_t *first, const int32_t *cou
 			continue;
 		}
 		const mbik::HostPlan &h = p->host;
-		const size_t l = ((size_t)h.spw * p->dev.lds_stride + p->dev.topo_words) * sizeof(float);
-		if (l > 160 * 1024) return fail(MBIK_EUNSUPPORTED, "skeleton too large for LDS at this lane count");
+		const size_t l = block_lds_bytes(p);
+		if (l > (size_t)mbik::kLdsBytes) return fail(MBIK_EUNSUPPORTED, "skeleton too large for LDS at this lane count");
 		lds = std::max(lds, l);
 		stab = stab || h.stabilization_passes > 0;
 		dp.push_back(p->dev);
@@ -1046,12 +1002,12 @@ int32_t mbik_group_solve(mbik_group *g, const int32_t *first, const int32_t *cou
 		blocks += (c + h.spw - 1) / h.spw;
 	}
 	if (ent.empty()) return MBIK_OK;
-	if (hipMemcpyAsync(g->d_plans, dp.data(), sizeof(DevPlan) * dp.size(), hipMemcpyHostToDevice, stream) != hipSuccess ||
-			hipMemcpyAsync(g->d_entries, ent.data(), sizeof(GroupEntry) * ent.size(), hipMemcpyHostToDevice, stream) != hipSuccess)
+	if (hipMemcpyAsync(g->d_plans.as<void>(), dp.data(), sizeof(DevPlan) * dp.size(), hipMemcpyHostToDevice, stream) != hipSuccess ||
+			hipMemcpyAsync(g->d_entries.as<void>(), ent.data(), sizeof(GroupEntry) * ent.size(), hipMemcpyHostToDevice, stream) != hipSuccess)
 		return fail(MBIK_EHIP, "hipMemcpyAsync group tables");
 	const mbik::GroupKernel kern = mbik::group_kernel(stab);
-	hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64), lds, stream, (const DevPlan *)g->d_plans,
-			(const GroupEntry *)g->d_entries, (int)ent.size());
+	hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64), lds, stream, g->d_plans.as<const DevPlan>(),
+			g->d_entries.as<const GroupEntry>(), (int)ent.size());
 	hipError_t e = hipGetLastError();
 	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("group launch failed: ") + hipGetErrorString(e));
 	// the staged tables above are pageable: hipMemcpyAsync has consumed them on return
@@ -1088,24 +1044,18 @@ int32_t mbik_solve_host(mbik_plan *p, int32_t first, int32_t count, const float 
 	DeviceGuard guard(p->device);
 	const mbik::HostPlan &h = p->host;
 	size_t need = (size_t)count;
-	if (need > p->scratch_skel) {
-		if (p->d_in) (void)hipFree(p->d_in);
-		if (p->d_tg) (void)hipFree(p->d_tg);
-		if (p->d_out) (void)hipFree(p->d_out);
-		p->d_in = p->d_tg = p->d_out = nullptr;
-		if (hipMalloc(&p->d_in, need * h.B * 10 * sizeof(float)) != hipSuccess ||
-				hipMalloc(&p->d_tg, std::max<size_t>(1, need * h.P * 12) * sizeof(float)) != hipSuccess ||
-				hipMalloc(&p->d_out, need * h.B * 10 * sizeof(float)) != hipSuccess)
-			return fail(MBIK_ENOMEM, "hipMalloc scratch");
-		p->scratch_skel = need;
-	}
-	if (hipMemcpy(p->d_in, pose_in, need * h.B * 10 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-			(h.P > 0 && hipMemcpy(p->d_tg, targets, need * h.P * 12 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))
+	if (p->h_in.reserve(need * h.B * 10 * sizeof(float), "hipMalloc scratch") ||
+			p->h_tg.reserve(std::max<size_t>(1, need * h.P * 12) * sizeof(float), "hipMalloc scratch") ||
+			p->h_out.reserve(need * h.B * 10 * sizeof(float), "hipMalloc scratch"))
+		return MBIK_ENOMEM;
+	float *d_in = p->h_in.as<float>(), *d_tg = p->h_tg.as<float>(), *d_out = p->h_out.as<float>();
+	if (hipMemcpy(d_in, pose_in, need * h.B * 10 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+			(h.P > 0 && hipMemcpy(d_tg, targets, need * h.P * 12 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))
 		return fail(MBIK_EHIP, "hipMemcpy H2D");
 	if (int rc = take_helper_timeout(p)) return rc;
-	int rc = launch(p, first, count, p->d_in, p->d_tg, p->d_out, nullptr, h.iterations, 0, h.NS - 1);
+	int rc = launch(p, first, count, d_in, d_tg, d_out, nullptr, h.iterations, 0, h.NS - 1);
 	if (rc) return rc;
-	if (hipMemcpy(pose_out, p->d_out, need * h.B * 10 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+	if (hipMemcpy(pose_out, d_out, need * h.B * 10 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
 		return fail(MBIK_EHIP, std::string("hipMemcpy D2H / kernel: ") + hipGetErrorString(hipGetLastError()));
 	return take_helper_timeout(p); // this launch's own (the copy waited for it)
 }
@@ -1119,7 +1069,7 @@ extern "C" int mbik_debug_replay(mbik_plan *p, int32_t mode, int32_t first, int3
 		const float *targets, float *pose_out, void *stream) {
 	DeviceGuard guard(p->device);
 	if (mode == 0) {
-		if (p->dev.rec_dump) (void)hipFree(p->dev.rec_dump);
+		p->rec_dump.reset();
 		p->dev.rec_dump = nullptr;
 		p->dev.replay = 0;
 		return MBIK_OK;
@@ -1129,20 +1079,14 @@ extern "C" int mbik_debug_replay(mbik_plan *p, int32_t mode, int32_t first, int3
 	if (!helper_on(p)) return fail(MBIK_EINVAL, "replay needs a helper-wave layout");
 	const mbik::HostPlan &h = p->host;
 	int per_iter = 0;
-	for (int r = 0; r < h.nrows; r++) {
-		int nq = 0;
-		for (int l = 0; l < h.K; l++) {
-			const int sg = h.sched[(size_t)r * h.K + l].seg;
-			if (sg >= 0) nq = std::max(nq, h.seg_bone_off[sg + 1] - h.seg_bone_off[sg]);
-		}
-		per_iter += nq;
-	}
+	for (int r = 0; r < h.nrows; r++) per_iter += mbik::row_max_steps(h, r);
 	const size_t blocks = (size_t)(count + h.spw - 1) / h.spw;
 	if (mode == 1) {
-		if (p->dev.rec_dump) (void)hipFree(p->dev.rec_dump);
+		p->rec_dump.reset();
+		p->dev.rec_dump = nullptr;
 		p->dev.rec_per_block = per_iter * h.iterations;
-		if (hipMalloc(&p->dev.rec_dump, blocks * p->dev.rec_per_block * kHelpF4 * 64 * sizeof(float4)) != hipSuccess)
-			return fail(MBIK_ENOMEM, "replay buffer");
+		if ((rc = p->rec_dump.reserve(blocks * p->dev.rec_per_block * kHelpF4 * 64 * sizeof(float4), "replay buffer")) != MBIK_OK) return rc;
+		p->dev.rec_dump = p->rec_dump.as<float4>();
 	}
 	p->dev.replay = mode;
 	rc = launch(p, first, count, pose_in, targets, pose_out, (hipStream_t)stream, h.iterations, 0, h.NS - 1);

@@ -243,9 +243,10 @@ int32_t mbik_selftest_math(int32_t device, uint64_t out[2]) {
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MBIK_ENODEV, "no HIP device");
 	if (device < 0 || device >= ndev) return fail(MBIK_EINVAL, "device out of range");
 	DeviceGuard guard(device);
-	unsigned long long *d = nullptr;
-	if (hipMalloc(&d, 2 * sizeof(unsigned long long)) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc");
-	int rc = MBIK_OK;
+	DevBuf buf;
+	int rc = buf.reserve(2 * sizeof(unsigned long long), "hipMalloc");
+	if (rc) return rc;
+	unsigned long long *d = buf.as<unsigned long long>();
 	if (hipMemset(d, 0, 2 * sizeof(unsigned long long)) != hipSuccess) rc = fail(MBIK_EHIP, "hipMemset");
 	if (rc == MBIK_OK) {
 		hipLaunchKernelGGL(mbik_selftest_math_kernel, dim3(8192), dim3(256), 0, 0, d);
@@ -253,26 +254,19 @@ int32_t mbik_selftest_math(int32_t device, uint64_t out[2]) {
 	}
 	unsigned long long h[2] = {0, 0};
 	if (rc == MBIK_OK && hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MBIK_EHIP, "hipMemcpy");
-	(void)hipFree(d);
 	out[0] = h[0];
 	out[1] = h[1];
 	return rc;
 }
 
-// A device buffer of n bytes holding the host data (or zeroed): the KAT entry points' staging.
 namespace {
-struct DevBuf {
-	void *p = nullptr;
-	~DevBuf() {
-		if (p) (void)hipFree(p);
-	}
-	int put(const void *h, size_t n) {
-		if (hipMalloc(&p, std::max<size_t>(n, 8)) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc");
-		if (h ? hipMemcpy(p, h, n, hipMemcpyHostToDevice) != hipSuccess : hipMemset(p, 0, std::max<size_t>(n, 8)) != hipSuccess)
-			return fail(MBIK_EHIP, "hipMemcpy");
-		return MBIK_OK;
-	}
-};
+// Makes b a device buffer of n bytes holding the host data (or zeroed): the KAT entry points' staging.
+int put(DevBuf &b, const void *h, size_t n) {
+	if (int rc = b.reserve(std::max<size_t>(n, 8), "hipMalloc")) return rc;
+	if (h ? hipMemcpy(b.as<void>(), h, n, hipMemcpyHostToDevice) != hipSuccess : hipMemset(b.as<void>(), 0, std::max<size_t>(n, 8)) != hipSuccess)
+		return fail(MBIK_EHIP, "hipMemcpy");
+	return MBIK_OK;
+}
 int kat_device(int32_t device) {
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MBIK_ENODEV, "no HIP device");
@@ -281,7 +275,7 @@ int kat_device(int32_t device) {
 }
 int kat_finish(void *dst, const DevBuf &b, size_t n) {
 	if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(MBIK_EHIP, "KAT kernel");
-	if (hipMemcpy(dst, b.p, n, hipMemcpyDeviceToHost) != hipSuccess) return fail(MBIK_EHIP, "hipMemcpy");
+	if (hipMemcpy(dst, b.as<void>(), n, hipMemcpyDeviceToHost) != hipSuccess) return fail(MBIK_EHIP, "hipMemcpy");
 	return MBIK_OK;
 }
 } // namespace
@@ -292,13 +286,13 @@ int32_t mbik_selftest_qcp(int32_t n, const float *moved, const float *target, co
 	if (int rc = kat_device(device)) return rc;
 	DeviceGuard guard(device);
 	DevBuf m, t, w, o;
-	int rc = m.put(moved, 12 * (size_t)n);
-	if (!rc) rc = t.put(target, 12 * (size_t)n);
-	if (!rc) rc = w.put(weights, 8 * (size_t)n);
-	if (!rc) rc = o.put(nullptr, 14 * sizeof(float));
+	int rc = put(m, moved, 12 * (size_t)n);
+	if (!rc) rc = put(t, target, 12 * (size_t)n);
+	if (!rc) rc = put(w, weights, 8 * (size_t)n);
+	if (!rc) rc = put(o, nullptr, 14 * sizeof(float));
 	if (rc) return rc;
-	hipLaunchKernelGGL(mbik_kat_qcp_kernel, dim3(1), dim3(64), 0, 0, (const float *)m.p, (const float *)t.p, (const double *)w.p, n,
-			translate, precision, (float *)o.p);
+	hipLaunchKernelGGL(mbik_kat_qcp_kernel, dim3(1), dim3(64), 0, 0, m.as<const float>(), t.as<const float>(), w.as<const double>(), n,
+			translate, precision, o.as<float>());
 	return kat_finish(out, o, 14 * sizeof(float));
 }
 
@@ -311,14 +305,14 @@ int32_t mbik_selftest_point_in_limits(const mbik_plan *p, int32_t slot, int32_t 
 	// the plan is only read here, never rescheduled, so a solve of it may be in flight
 	if (!p->dev.topo_blob) return fail(MBIK_EHIP, "plan has no topology blob");
 	DevBuf o, ib;
-	int rc = o.put(nullptr, 6 * sizeof(float));
-	if (!rc) rc = ib.put(nullptr, 2 * sizeof(double));
+	int rc = put(o, nullptr, 6 * sizeof(float));
+	if (!rc) rc = put(ib, nullptr, 2 * sizeof(double));
 	if (rc) return rc;
 	DevPlan d = p->dev; // the plain [item][field][N] tables (kTab64)
-	hipLaunchKernelGGL(mbik_kat_limits_kernel, dim3(1), dim3(64), 0, 0, d, slot, skeleton, point[0], point[1], point[2], (float *)o.p,
-			(double *)ib.p);
+	hipLaunchKernelGGL(mbik_kat_limits_kernel, dim3(1), dim3(64), 0, 0, d, slot, skeleton, point[0], point[1], point[2], o.as<float>(),
+			ib.as<double>());
 	if ((rc = kat_finish(out, o, 6 * sizeof(float))) != MBIK_OK) return rc;
-	if (hipMemcpy(in_bounds, ib.p, 2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(MBIK_EHIP, "hipMemcpy");
+	if (hipMemcpy(in_bounds, ib.as<void>(), 2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(MBIK_EHIP, "hipMemcpy");
 	return MBIK_OK;
 }
 
@@ -327,11 +321,11 @@ int32_t mbik_selftest_xform(int32_t op, const float a[12], const float b[12], in
 	if (int rc = kat_device(device)) return rc;
 	DeviceGuard guard(device);
 	DevBuf da, db, o;
-	int rc = da.put(a, 12 * sizeof(float));
-	if (!rc) rc = db.put(op == 0 ? b : a, 12 * sizeof(float));
-	if (!rc) rc = o.put(nullptr, 12 * sizeof(float));
+	int rc = put(da, a, 12 * sizeof(float));
+	if (!rc) rc = put(db, op == 0 ? b : a, 12 * sizeof(float));
+	if (!rc) rc = put(o, nullptr, 12 * sizeof(float));
 	if (rc) return rc;
-	hipLaunchKernelGGL(mbik_kat_xform_kernel, dim3(1), dim3(64), 0, 0, op, (const float *)da.p, (const float *)db.p, (float *)o.p);
+	hipLaunchKernelGGL(mbik_kat_xform_kernel, dim3(1), dim3(64), 0, 0, op, da.as<const float>(), db.as<const float>(), o.as<float>());
 	return kat_finish(out, o, 12 * sizeof(float));
 }
 
@@ -341,9 +335,10 @@ int32_t mbik_selftest_div(int32_t device, uint64_t random_iterations, uint64_t o
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MBIK_ENODEV, "no HIP device");
 	if (device < 0 || device >= ndev) return fail(MBIK_EINVAL, "device out of range");
 	DeviceGuard guard(device);
-	unsigned long long *d = nullptr;
-	if (hipMalloc(&d, 20 * sizeof(unsigned long long)) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc");
-	int rc = MBIK_OK;
+	DevBuf buf;
+	int rc = buf.reserve(20 * sizeof(unsigned long long), "hipMalloc");
+	if (rc) return rc;
+	unsigned long long *d = buf.as<unsigned long long>();
 	if (hipMemset(d, 0, 20 * sizeof(unsigned long long)) != hipSuccess) rc = fail(MBIK_EHIP, "hipMemset");
 	auto run = [&](int cls, int sel) {
 		if (rc != MBIK_OK) return;
@@ -359,7 +354,6 @@ int32_t mbik_selftest_div(int32_t device, uint64_t random_iterations, uint64_t o
 	if (rc == MBIK_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(MBIK_EHIP, "self-test kernel");
 	unsigned long long h[20] = {};
 	if (rc == MBIK_OK && hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MBIK_EHIP, "hipMemcpy");
-	(void)hipFree(d);
 	for (int i = 0; i < 20; i++) out[i] = h[i];
 	return rc;
 }
@@ -374,10 +368,11 @@ int32_t mbik_selftest_libm(int32_t fn, uint64_t first, uint64_t count, const dou
 	out[2] = 0;
 	if (count == 0) return MBIK_OK;
 	hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-	unsigned long long *d = nullptr;
-	if (hipMalloc(&d, 3 * sizeof(unsigned long long)) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc");
+	DevBuf buf;
+	int rc = buf.reserve(3 * sizeof(unsigned long long), "hipMalloc");
+	if (rc) return rc;
+	unsigned long long *d = buf.as<unsigned long long>();
 	unsigned long long h[3] = {0, ~0ull, 0};
-	int rc = MBIK_OK;
 	if (hipMemcpyAsync(d, h, sizeof(h), hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(MBIK_EHIP, "hipMemcpyAsync");
 	if (rc == MBIK_OK) {
 		hipLaunchKernelGGL(mbik_selftest_libm_kernel, dim3(4096), dim3(256), 0, st, (int)fn, first, count, inputs, expected, d);
@@ -385,7 +380,6 @@ int32_t mbik_selftest_libm(int32_t fn, uint64_t first, uint64_t count, const dou
 	}
 	if (rc == MBIK_OK && hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(MBIK_EHIP, "hipMemcpyAsync");
 	if (rc == MBIK_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(MBIK_EHIP, "self-test kernel");
-	(void)hipFree(d);
 	out[0] = h[0];
 	out[1] = h[1];
 	out[2] = h[2];

@@ -16,7 +16,7 @@ struct mbik_mesh {
 	int32_t B = 0, V = 0, K = 4;
 	bool normals = false;
 	int32_t P = 0, mode = 0;         // shapes (P == 0: a mesh without)
-	unsigned char *d_mesh = nullptr; // skin_layout()'s planes, then morph_layout()'s
+	DevBuf mesh;                     // skin_layout()'s planes, then morph_layout()'s
 };
 
 namespace {
@@ -32,11 +32,6 @@ constexpr int64_t kSkinBlockLdsTarget = MBIK_SKIN_LDS_TARGET_KIB * 1024;
 constexpr int kSkinMaxSkeletonsPerBlock = 16;
 // Blocks the grid aims for before it stops splitting the vertex range: eight per CU.
 constexpr int kSkinBlocksPerCu = 8;
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-	return x < y + nb && y < x + na;
-}
 
 struct SkinShape {
 	int S, chunk, chunks, vshift;
@@ -124,28 +119,21 @@ int create_mesh(int32_t bone_count, int32_t vertex_count, int32_t influences, co
 	if (shaped)
 		if (int rc = check_shapes(bone_count, vertex_count, normals != nullptr, shapes, mbik::kSkinMaxLdsBytes)) return rc;
 	if (int rc = check_mesh(bone_count, vertex_count, influences, positions, bone_indices, weights)) return rc;
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MBIK_ENODEV, "no HIP device visible");
-	if (device < 0 || device >= ndev) return fail(MBIK_EINVAL, "device index out of range");
+	if (int rc = check_device(device)) return rc;
 	std::unique_ptr<mbik_mesh> m(new mbik_mesh());
 	m->device = device, m->B = bone_count, m->V = vertex_count, m->K = influences, m->normals = normals != nullptr;
 	if (shaped) m->P = shapes->shape_count, m->mode = shapes->mode;
 	DeviceGuard guard(device);
-	int cus = 0;
-	if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) m->cu_count = cus;
+	m->cu_count = cu_count_of(device);
 	if (vertex_count > 0) {
 		const mbik::SkinLayout l = mbik::skin_layout(vertex_count, influences, m->normals);
 		const int64_t bytes = shaped ? mbik::morph_layout(vertex_count, influences, m->normals, m->P).bytes : l.bytes;
 		std::vector<unsigned char> packed((size_t)bytes);
 		mbik::skin_pack(vertex_count, influences, positions, normals, bone_indices, weights, packed.data());
 		if (shaped) mbik::morph_pack(vertex_count, influences, m->P, shapes->positions, shapes->normals, packed.data());
-		void *d = nullptr;
-		if (hipMalloc(&d, packed.size()) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc failed for the mesh");
-		m->d_mesh = static_cast<unsigned char *>(d);
-		if (hipMemcpy(d, packed.data(), packed.size(), hipMemcpyHostToDevice) != hipSuccess) {
-			(void)hipFree(d);
+		if (int rc = m->mesh.reserve(packed.size(), "hipMalloc failed for the mesh")) return rc;
+		if (hipMemcpy(m->mesh.as<void>(), packed.data(), packed.size(), hipMemcpyHostToDevice) != hipSuccess)
 			return fail(MBIK_EHIP, "hipMemcpy failed for the mesh");
-		}
 	}
 	*out_mesh = m.release();
 	return MBIK_OK;
@@ -166,14 +154,7 @@ int32_t mbik_mesh_create_shaped(int32_t bone_count, int32_t vertex_count, int32_
 	return create_mesh(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, true, shapes, device, out_mesh);
 }
 
-void mbik_mesh_destroy(mbik_mesh *m) {
-	if (!m) return;
-	if (m->d_mesh) {
-		DeviceGuard guard(m->device);
-		(void)hipFree(m->d_mesh);
-	}
-	delete m;
-}
+void mbik_mesh_destroy(mbik_mesh *m) { delete m; }
 
 int32_t mbik_mesh_launch_shape(const mbik_mesh *m, int32_t count, int32_t *skeletons_per_block, int32_t *vertex_chunks) {
 	if (!m) return fail(MBIK_EINVAL, "null mesh");
@@ -192,7 +173,7 @@ int32_t mbik_skin_vertices(mbik_mesh *m, int32_t count, const float *skin, float
 	DeviceGuard guard(m->device);
 	const SkinShape sh = shape_of(m, count, false);
 	hipError_t e = mbik::launch_skin(reinterpret_cast<hipStream_t>(hip_stream), m->K, count, m->B, m->V, sh.S, sh.chunk, sh.chunks,
-			sh.vshift, m->d_mesh, m->normals, skin, out_positions, out_normals);
+			sh.vshift, m->mesh.as<unsigned char>(), m->normals, skin, out_positions, out_normals);
 	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("skinning launch failed: ") + hipGetErrorString(e));
 	return MBIK_OK;
 }
@@ -207,7 +188,7 @@ int32_t mbik_skin_vertices_shaped(mbik_mesh *m, int32_t count, const float *skin
 	DeviceGuard guard(m->device);
 	const SkinShape sh = shape_of(m, count, true);
 	hipError_t e = mbik::launch_skin_shaped(reinterpret_cast<hipStream_t>(hip_stream), m->K, m->mode, count, m->B, m->V, m->P, sh.S,
-			sh.chunk, sh.chunks, sh.vshift, m->d_mesh, m->normals, skin, shape_weights, out_positions, out_normals);
+			sh.chunk, sh.chunks, sh.vshift, m->mesh.as<unsigned char>(), m->normals, skin, shape_weights, out_positions, out_normals);
 	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("shaped skinning launch failed: ") + hipGetErrorString(e));
 	return MBIK_OK;
 }

@@ -64,7 +64,7 @@ int build_topologies(int n, const mbik_skeleton_desc *descs, const mbik_config *
 		std::copy(chd.begin(), chd.begin() + B, hin_d.data() + in_d[i]);
 	}
 	// the slices, pointing into device buffers (or into host buffers when device < 0)
-	char *dbase = nullptr;
+	DevBuf dbuf;
 	std::vector<int32_t> hscr_i;
 	std::vector<double> hscr_d;
 	const size_t b_in_i = hin_i.size() * 4, b_in_f = hin_f.size() * 4, b_in_d = hin_d.size() * 8, b_o_i = hout_i.size() * 4,
@@ -76,11 +76,13 @@ int build_topologies(int n, const mbik_skeleton_desc *descs, const mbik_config *
 				 off_s_d = off_s_i + a16(b_s_i), off_sl = off_s_d + a16(b_s_d), total = off_sl + a16(b_sl);
 	const bool on_device = device >= 0;
 	if (on_device) {
-		if (hipMalloc(&dbase, total) != hipSuccess) return fail(MBIK_ENOMEM, "hipMalloc topology build");
+		DeviceGuard guard(device);
+		if (int rc = dbuf.reserve(total, "hipMalloc topology build")) return rc;
 	} else {
 		hscr_i.assign(s_i[n] + 4, 0);
 		hscr_d.assign(s_d[n] + 4, 0.0);
 	}
+	char *dbase = dbuf.as<char>();
 	auto P_i = [&](size_t off, std::vector<int32_t> &h) { return on_device ? reinterpret_cast<int32_t *>(dbase + off) : h.data(); };
 	auto P_f = [&](size_t off, std::vector<float> &h) { return on_device ? reinterpret_cast<float *>(dbase + off) : h.data(); };
 	auto P_d = [&](size_t off, std::vector<double> &h) { return on_device ? reinterpret_cast<double *>(dbase + off) : h.data(); };
@@ -114,23 +116,17 @@ int build_topologies(int n, const mbik_skeleton_desc *descs, const mbik_config *
 	}
 	if (on_device) {
 		DeviceGuard guard(device);
-		int rc = MBIK_OK;
 		if (hipMemcpy(dbase, hin_i.data(), b_in_i, hipMemcpyHostToDevice) != hipSuccess ||
 				hipMemcpy(dbase + off_in_f, hin_f.data(), b_in_f, hipMemcpyHostToDevice) != hipSuccess ||
 				hipMemcpy(dbase + off_in_d, hin_d.data(), b_in_d, hipMemcpyHostToDevice) != hipSuccess ||
 				hipMemcpy(dbase + off_sl, slices.data(), b_sl, hipMemcpyHostToDevice) != hipSuccess)
-			rc = fail(MBIK_EHIP, "hipMemcpy topology inputs");
-		if (rc == MBIK_OK) {
-			if (mbik::launch_topology(reinterpret_cast<const TopoSlice *>(dbase + off_sl), n) != hipSuccess ||
-					hipDeviceSynchronize() != hipSuccess)
-				rc = fail(MBIK_EHIP, "topology kernel");
-		}
-		if (rc == MBIK_OK && (hipMemcpy(hout_i.data(), dbase + off_o_i, b_o_i, hipMemcpyDeviceToHost) != hipSuccess ||
-								 hipMemcpy(hout_f.data(), dbase + off_o_f, b_o_f, hipMemcpyDeviceToHost) != hipSuccess ||
-								 hipMemcpy(hout_d.data(), dbase + off_o_d, b_o_d, hipMemcpyDeviceToHost) != hipSuccess))
-			rc = fail(MBIK_EHIP, "hipMemcpy topology outputs");
-		(void)hipFree(dbase);
-		if (rc) return rc;
+			return fail(MBIK_EHIP, "hipMemcpy topology inputs");
+		if (mbik::launch_topology(reinterpret_cast<const TopoSlice *>(dbase + off_sl), n) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+			return fail(MBIK_EHIP, "topology kernel");
+		if (hipMemcpy(hout_i.data(), dbase + off_o_i, b_o_i, hipMemcpyDeviceToHost) != hipSuccess ||
+				hipMemcpy(hout_f.data(), dbase + off_o_f, b_o_f, hipMemcpyDeviceToHost) != hipSuccess ||
+				hipMemcpy(hout_d.data(), dbase + off_o_d, b_o_d, hipMemcpyDeviceToHost) != hipSuccess)
+			return fail(MBIK_EHIP, "hipMemcpy topology outputs");
 	} else {
 		for (int i = 0; i < n; i++) {
 			const mbik::TopoRig &r = slices[i].rig;
@@ -154,11 +150,8 @@ extern "C" {
 int32_t mbik_selftest_topology(int32_t n_rigs, const mbik_skeleton_desc *descs, const mbik_config *configs, int32_t device,
 		int32_t *mismatches) {
 	if (n_rigs < 0 || (n_rigs > 0 && (!descs || !configs || !mismatches))) return fail(MBIK_EINVAL, "null argument");
-	if (device >= 0) {
-		int ndev = 0;
-		if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MBIK_ENODEV, "no HIP device visible");
-		if (device >= ndev) return fail(MBIK_EINVAL, "device index out of range");
-	}
+	if (device >= 0)
+		if (int rc = check_device(device)) return rc;
 	std::vector<mbik::HostPlan> built;
 	std::vector<std::string> errs;
 	const int rc = build_topologies(n_rigs, descs, configs, device, built, errs);
@@ -194,9 +187,7 @@ int32_t mbik_plan_create_device_opts(int32_t n_rigs, const mbik_skeleton_desc *d
 	for (int i = 0; i < n_rigs; i++) out_plans[i] = nullptr;
 	int libm = 0;
 	if (read_options(opts, libm)) return MBIK_EINVAL;
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MBIK_ENODEV, "no HIP device visible");
-	if (device < 0 || device >= ndev) return fail(MBIK_EINVAL, "device index out of range");
+	if (int rc = check_device(device)) return rc;
 	for (int i = 0; i < n_rigs; i++)
 		if (n_skeletons[i] <= 0 || !setup_pose[i]) return fail(MBIK_EINVAL, "n_skeletons must be > 0 and setup_pose non-null");
 	std::vector<mbik::HostPlan> built;
@@ -225,20 +216,17 @@ int32_t mbik_plan_create_device_opts(int32_t n_rigs, const mbik_skeleton_desc *d
 		h.libm_variant = libm;
 		h.N = n_skeletons[i];
 		const size_t N = (size_t)h.N;
-		h.D.assign((size_t)h.B * 9 * N, 0.0f); // filled on the device below (mbik_setup_kernel)
-		h.CF.assign((size_t)h.NC * h.cf_stride() * N, 0.0f);
-		h.CD.assign((size_t)h.NC * h.cd_stride() * N, 0.0);
+		h.D.assign(h.d_floats(N), 0.0f); // filled on the device below (mbik_setup_kernel)
+		h.CF.assign(h.cf_floats(N), 0.0f);
+		h.CD.assign(h.cd_doubles(N), 0.0);
 		mbik::setup_tables(h);
 		h.setup_max_cones = std::max(1, d.max_cones);
-		rc = finish_plan(p.get(), setup_pose[i], nullptr); // (frees what it took when it fails)
+		rc = finish_plan(p.get(), setup_pose[i], nullptr);
 		if (rc == MBIK_OK)
 			rc = mbik_plan_rebuild_setup(p.get(), 0, h.N, setup_pose[i], h.NC ? cones[i] : nullptr, h.NC ? twist[i] : nullptr, nullptr);
-		plans.push_back(std::move(p)); // released through mbik_plan_destroy below on any failure
+		plans.push_back(std::move(p));
 	}
-	if (rc) {
-		for (auto &p : plans) mbik_plan_destroy(p.release());
-		return rc;
-	}
+	if (rc) return rc; // (`plans` deletes every plan made so far, which frees what each took)
 	for (int i = 0; i < n_rigs; i++) out_plans[i] = plans[i].release();
 	return MBIK_OK;
 }
@@ -290,10 +278,8 @@ struct PlanReader {
 		return v;
 	}
 };
-size_t cmode_state_bytes(const mbik_plan *p) {
-	const mbik::HostPlan &h = p->host;
-	return (size_t)(3 * h.B + 2 * h.NC) * 12 * (size_t)h.N * sizeof(float) + 4 * (size_t)p->cm.W * (size_t)h.N * sizeof(uint32_t);
-}
+// constraint_mode's state in a plan file: the node caches in the plain order, then the dirty words
+size_t cmode_state_bytes(const mbik::HostPlan &h) { return cmode_file_node_bytes(h) + cmode_dirty_bytes(h); }
 } // namespace
 extern "C" {
 
@@ -319,8 +305,8 @@ int32_t mbik_plan_save(const mbik_plan *p, void *buf, uint64_t capacity, uint64_
 	w.vec(p->src_bone_damp);
 	w.put<int32_t>(h.setup_max_cones);
 	const size_t N = (size_t)h.N;
-	std::vector<float> D((size_t)h.B * 9 * N), CF((size_t)h.NC * h.cf_stride() * N);
-	std::vector<double> CD((size_t)h.NC * h.cd_stride() * N);
+	std::vector<float> D(h.d_floats(N)), CF(h.cf_floats(N));
+	std::vector<double> CD(h.cd_doubles(N));
 	if ((!D.empty() && hipMemcpy(D.data(), p->dev.D, D.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) ||
 			(!CF.empty() && hipMemcpy(CF.data(), p->dev.CF, CF.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) ||
 			(!CD.empty() && hipMemcpy(CD.data(), p->dev.CD, CD.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
@@ -328,14 +314,14 @@ int32_t mbik_plan_save(const mbik_plan *p, void *buf, uint64_t capacity, uint64_
 	w.vec(D);
 	w.vec(CF);
 	w.vec(CD);
-	for (int32_t v : {p->lanes_override, p->spw_override, p->interval_override, p->staging_override, p->locals_override,
-				 p->waves_override, p->cm_lanes, p->tab64, p->cm_spw_div})
+	const LayoutPins &pn = p->pins;
+	for (int32_t v : {pn.lanes, pn.spw, pn.interval, pn.staging, pn.locals, pn.waves, pn.cm_lanes, p->tab64, pn.cm_spw_div})
 		w.put<int32_t>(v);
 	std::vector<char> cm;
 	if (h.constraint_mode && N) {
-		cm.resize(cmode_state_bytes(p));
+		cm.resize(cmode_state_bytes(h));
 		const size_t node_bytes = cmode_file_node_bytes(h);
-		std::vector<float> tiled(node_area_floats(3 * h.B + 2 * h.NC, N));
+		std::vector<float> tiled(cmode_node_bytes(h) / sizeof(float));
 		if (hipMemcpy(tiled.data(), p->cm.node, tiled.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
 				hipMemcpy(cm.data() + node_bytes, p->cm.dirty, cm.size() - node_bytes, hipMemcpyDeviceToHost) != hipSuccess)
 			return fail(MBIK_EHIP, "hipMemcpy constraint_mode state");
@@ -343,8 +329,8 @@ int32_t mbik_plan_save(const mbik_plan *p, void *buf, uint64_t capacity, uint64_
 	}
 	w.vec(cm);
 	w.put<int32_t>(h.libm_variant); // format 3
-	w.put<int32_t>(p->helper_override); // format 4
-	w.put<int32_t>(p->roles_override); // format 5
+	w.put<int32_t>(pn.helper); // format 4
+	w.put<int32_t>(pn.roles); // format 5
 	*size = w.b.size();
 	if (!buf) return MBIK_OK;
 	if (capacity < w.b.size()) return fail(MBIK_EINVAL, "buffer smaller than the saved plan (see *size)");
@@ -355,9 +341,7 @@ int32_t mbik_plan_save(const mbik_plan *p, void *buf, uint64_t capacity, uint64_
 int32_t mbik_plan_load(const void *buf, uint64_t size, int32_t device, mbik_plan **out_plan) {
 	if (!buf || !out_plan) return fail(MBIK_EINVAL, "null argument");
 	*out_plan = nullptr;
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MBIK_ENODEV, "no HIP device visible");
-	if (device < 0 || device >= ndev) return fail(MBIK_EINVAL, "device index out of range");
+	if (int rc = check_device(device)) return rc;
 	PlanReader r{static_cast<const char *>(buf), static_cast<const char *>(buf) + size};
 	char magic[8];
 	if (!r.bytes(magic, 8) || std::memcmp(magic, kPlanMagic, 8) != 0) return fail(MBIK_EINVAL, "not a saved mbik plan");
@@ -409,30 +393,27 @@ int32_t mbik_plan_load(const void *buf, uint64_t size, int32_t device, mbik_plan
 	h.libm_variant = libm;
 	h.N = N;
 	const size_t n = (size_t)N;
-	if (D.size() != (size_t)h.B * 9 * n || CF.size() != (size_t)h.NC * h.cf_stride() * n ||
-			CD.size() != (size_t)h.NC * h.cd_stride() * n)
+	if (D.size() != h.d_floats(n) || CF.size() != h.cf_floats(n) || CD.size() != h.cd_doubles(n))
 		return fail(MBIK_EINVAL, "saved plan tables do not match its topology");
 	mbik::setup_tables(h);
 	h.setup_max_cones = std::max(1, setup_max_cones);
 	h.D = std::move(D);
 	h.CF = std::move(CF);
 	h.CD = std::move(CD);
-	p->lanes_override = ov[0];
-	p->spw_override = ov[1];
-	p->interval_override = ov[2];
-	p->staging_override = ov[3];
-	p->locals_override = ov[4];
-	p->waves_override = ov[5];
-	p->cm_lanes = ov[6];
+	LayoutPins &pn = p->pins;
+	pn.lanes = ov[0];
+	pn.spw = ov[1];
+	pn.interval = ov[2];
+	pn.staging = ov[3];
+	pn.locals = ov[4];
+	pn.waves = ov[5];
+	pn.cm_lanes = ov[6];
 	p->tab64 = ov[7] != 0;
-	p->cm_spw_div = std::max(0, std::min(6, ov[8]));
-	p->helper_override = helper;
-	p->roles_override = roles;
-	if (h.constraint_mode) {
-		const int W = std::max(1, (h.cm_npos + 31) / 32);
-		const size_t want = (size_t)(3 * h.B + 2 * h.NC) * 12 * n * sizeof(float) + 4 * (size_t)W * n * sizeof(uint32_t);
-		if (cm.size() != want) return fail(MBIK_EINVAL, "saved constraint_mode state does not match its topology");
-	}
+	pn.cm_spw_div = std::max(0, std::min(6, ov[8]));
+	pn.helper = helper;
+	pn.roles = roles;
+	if (h.constraint_mode && cm.size() != cmode_state_bytes(h))
+		return fail(MBIK_EINVAL, "saved constraint_mode state does not match its topology");
 	DeviceGuard guard(device);
 	const int rc = finish_plan(p.get(), nullptr, h.constraint_mode ? cm.data() : nullptr);
 	if (rc) return rc;

@@ -14,7 +14,7 @@ CmodeKernel cmode_kernel(bool stab, bool nb32, bool chain) {
 	std::call_once(once, [] {
 		for (auto &a : ks)
 			for (auto &b : a)
-				for (CmodeKernel k : b) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+				for (CmodeKernel k : b) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
 	});
 	return ks[stab ? 1 : 0][nb32 ? 1 : 0][chain ? 1 : 0];
 }
@@ -26,7 +26,7 @@ CmodeKernel cmode_kernel_rw(bool chain, int kw) {
 	static std::once_flag once;
 	std::call_once(once, [] {
 		for (auto &row : krw)
-			for (CmodeKernel k : row) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+			for (CmodeKernel k : row) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
 	});
 	return krw[chain ? 1 : 0][kw == 2 ? 0 : kw == 4 ? 1 : 2];
 }

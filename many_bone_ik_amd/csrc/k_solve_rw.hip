@@ -52,7 +52,7 @@ SolveKernel solve_kernel_rw(int kw, int wpe, int pm) {
 	static std::once_flag once;
 	std::call_once(once, [] {
 		for (auto &row : krw)
-			for (SolveKernel k : row) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+			for (SolveKernel k : row) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
 	});
 	const int i = kw == 2 ? (wpe == 2 ? 1 : 0) : kw == 4 ? (wpe == 2 ? 3 : 2) : 4;
 	return krw[pm == kPrioDefault ? 1 : 0][i];
@@ -61,13 +61,13 @@ SolveKernel solve_kernel_rw(int kw, int wpe, int pm) {
 SolveKernel solve_kernel_help(int pm, bool replay) {
 	static std::once_flag once;
 	std::call_once(once, [] {
-		(void)hipFuncSetAttribute((const void *)mbik_solve_kernel_help<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+		(void)hipFuncSetAttribute((const void *)mbik_solve_kernel_help<0>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
 		(void)hipFuncSetAttribute((const void *)mbik_solve_kernel_help<kPrioDefault>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				160 * 1024);
+				kLdsBytes);
 #ifdef MBIK_REPLAY
-		(void)hipFuncSetAttribute((const void *)mbik_solve_kernel_replay<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+		(void)hipFuncSetAttribute((const void *)mbik_solve_kernel_replay<0>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
 		(void)hipFuncSetAttribute((const void *)mbik_solve_kernel_replay<kPrioDefault>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				160 * 1024);
+				kLdsBytes);
 #endif
 	});
 #ifdef MBIK_REPLAY

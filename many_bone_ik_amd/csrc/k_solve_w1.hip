@@ -42,9 +42,9 @@ SolveKernel solve_kernel_w1(bool stab, int pl, bool t32, int pm) {
 	static std::once_flag once;
 	std::call_once(once, [] {
 		for (auto &row : ks)
-			for (SolveKernel k : row) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		for (SolveKernel k : k64) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		for (SolveKernel k : kd) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+			for (SolveKernel k : row) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+		for (SolveKernel k : k64) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+		for (SolveKernel k : kd) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
 	});
 	if (!t32) return k64[stab ? 1 : 0];
 	if (stab) return ks[1][pl];
@@ -54,8 +54,8 @@ SolveKernel solve_kernel_w1(bool stab, int pl, bool t32, int pm) {
 GroupKernel group_kernel(bool stab) {
 	static std::once_flag once;
 	std::call_once(once, [] {
-		(void)hipFuncSetAttribute((const void *)mbik_group_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		(void)hipFuncSetAttribute((const void *)mbik_group_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+		(void)hipFuncSetAttribute((const void *)mbik_group_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+		(void)hipFuncSetAttribute((const void *)mbik_group_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
 	});
 	return stab ? mbik_group_kernel<true> : mbik_group_kernel<false>;
 }

@@ -20,8 +20,8 @@ SolveKernel solve_kernel_w2(int pl, bool t32, bool xs, int pm) {
 	static std::once_flag once;
 	std::call_once(once, [] {
 		for (const SolveKernel *a : {k2, k2x, k2d, k2xd})
-			for (int i = 0; i < 3; i++) (void)hipFuncSetAttribute((const void *)a[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		(void)hipFuncSetAttribute((const void *)k64, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+			for (int i = 0; i < 3; i++) (void)hipFuncSetAttribute((const void *)a[i], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+		(void)hipFuncSetAttribute((const void *)k64, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
 	});
 	if (!t32) return k64;
 	const bool dflt = pm == kPrioDefault;

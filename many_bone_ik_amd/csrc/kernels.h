@@ -83,10 +83,6 @@ struct DevPlan {
 // specialised mask is the reference's default priorities (0.2, 0, 0.2)
 // (ik_effector_template_3d.h:45): origin, +/-x, +/-z.
 constexpr int kPrioDefault = 1 | (6 << 0) | (6 << 4);
-// Skeleton tiles of the locals / checkpoint globals in device memory (LocTiled) and of the
-// setup-table copy (row_at<kTabTiled>).
-constexpr int kLocTile = 16;
-constexpr int kRowTile = 16;
 // Helper-wave ring (bone_step.h): kHelpSlots records of kHelpF4 float4 per lane, plus counters.
 constexpr int kHelpF4 = 18, kHelpSlots = 4;
 constexpr int kHelpRingBytes = kHelpSlots * kHelpF4 * 64 * 16 + 32;

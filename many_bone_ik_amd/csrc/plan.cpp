@@ -871,8 +871,8 @@ void build_schedule(HostPlan &p, int32_t lanes, int64_t nlaunch, int32_t spw_ove
 	};
 	auto resident = [&](int spw) -> int64_t {
 		const int64_t block = spw * (int64_t)(((lds_floats_per_skeleton(p) + 3) & ~3) * 4) + topo;
-		if (block > 160 * 1024) return 0;
-		const int64_t blocks = blocks_per_cu ? blocks_per_cu(ctx, block) : 160 * 1024 / block;
+		if (block > kLdsBytes) return 0;
+		const int64_t blocks = blocks_per_cu ? blocks_per_cu(ctx, block) : kLdsBytes / block;
 		return blocks * spw;
 	};
 	set_interval(interval_override > 0 ? interval_override : 1);
@@ -921,8 +921,20 @@ void build_schedule(HostPlan &p, int32_t lanes, int64_t nlaunch, int32_t spw_ove
 		r[3] = c0 | ((c1 - c0) << 16);
 	}
 	p.spw = best;
-	p.lds_block_bytes = best * (int64_t)(((lds_floats_per_skeleton(p) + 3) & ~3) * 4) + topo +
-			(p.wave_roles ? 64 * 4 + (p.rw_xslots ? ((int64_t)p.P + p.rw_xslots) * 12 * 64 * 4 + rw_record_bytes(p) : 0) : 0);
+	p.lds_block_bytes = best * (int64_t)(((lds_floats_per_skeleton(p) + 3) & ~3) * 4) + topo + (p.wave_roles ? rw_extra_lds_bytes(p) : 0);
+}
+
+int64_t rw_extra_lds_bytes(const HostPlan &p) {
+	return 64 * 4 + (p.rw_xslots ? ((int64_t)p.P + p.rw_xslots) * 12 * 64 * 4 + rw_record_bytes(p) : 0);
+}
+
+int row_max_steps(const HostPlan &p, int row) {
+	int n = 0;
+	for (int l = 0; l < p.K; l++) {
+		const int sg = p.sched[(size_t)row * p.K + l].seg;
+		if (sg >= 0) n = std::max(n, p.seg_bone_off[sg + 1] - p.seg_bone_off[sg]);
+	}
+	return n;
 }
 
 int64_t rw_record_bytes(const HostPlan &p) {

@@ -3,6 +3,8 @@
 // plus each skeleton's setup-dependent tables (bone directions, Kusudama frames).
 #pragma once
 
+#include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -64,6 +66,14 @@ constexpr int CD_PER_CONE = 2;
 #ifndef MBIK_RW_PERM
 #define MBIK_RW_PERM 1
 #endif
+
+// LDS of a CU: what a block of the solve path may take (every solve kernel handle has its
+// dynamic-LDS attribute set to it).
+constexpr int64_t kLdsBytes = 160 * 1024;
+// Skeleton tiles of the locals / checkpoint globals in device memory (LocTiled) and of the
+// setup-table copy (row_at<kTabTiled>).
+constexpr int kLocTile = 16;
+constexpr int kRowTile = 16;
 
 struct SchedTask {
 	int32_t seg;  // -1 idle
@@ -182,6 +192,16 @@ struct HostPlan {
 
 	int cf_stride() const { return CF_CONE0 + CF_PER_CONE * max_cones; }
 	int cd_stride() const { return CD_PER_CONE * max_cones; }
+	// Element counts of D / CF / CD for n skeletons; the skeleton-tiled copies hold padded_n().
+	size_t d_floats(size_t n) const { return (size_t)B * 9 * n; }
+	size_t cf_floats(size_t n) const { return (size_t)NC * cf_stride() * n; }
+	size_t cd_doubles(size_t n) const { return (size_t)NC * cd_stride() * n; }
+	size_t padded_n() const { return ((size_t)N + kRowTile - 1) / kRowTile * kRowTile; }
+	// constraint_mode node caches (cmode.h): node slots -- pose local, pose global and bone-direction
+	// global per bone, constraint-orientation and twist global per constraint -- and the dirty words
+	// of one kind.
+	int cm_slots() const { return 3 * B + 2 * NC; }
+	int cm_dirty_words() const { return std::max(1, (cm_npos + 31) / 32); }
 };
 
 // Builds the topology tables; returns an empty string on success, else the error.
@@ -226,5 +246,10 @@ int64_t topology_bytes(const HostPlan &plan);
 // groups' counters (rw_wait), after the effector-global exchange; 0 without cooperative rows.
 constexpr int kRwRecF4 = 9;
 int64_t rw_record_bytes(const HostPlan &plan);
+// Wave roles: what a block's LDS holds beyond the classic block's -- the non-finite flags and, with
+// cooperative rows, the targets, the effector-global exchange and the groups' records.
+int64_t rw_extra_lds_bytes(const HostPlan &plan);
+// The longest segment of schedule row `row`, in bone-steps.
+int row_max_steps(const HostPlan &plan, int row);
 
 } // namespace mbik
