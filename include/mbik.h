@@ -57,7 +57,7 @@ extern "C" {
 #define MBIK_EUNSUPPORTED (-4)
 #define MBIK_ENODEV (-5)
 
-#define MBIK_ABI_VERSION 13
+#define MBIK_ABI_VERSION 14
 
 typedef struct mbik_plan mbik_plan;
 typedef struct mbik_group mbik_group;
@@ -615,6 +615,96 @@ int32_t mbik_skin_vertices_shaped(mbik_mesh *mesh, int32_t count, const float *s
 int32_t mbik_skin_vertices_shaped_cpu(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
 		const float *normals, const int32_t *bone_indices, const float *weights, const mbik_mesh_shapes *shapes, int32_t count,
 		const float *skin, const float *shape_weights, float *out_positions, float *out_normals);
+
+/* Skeleton bounds and frustum culling (ABI 14): which skeletons of a batch can be seen, decided on
+ * the device from the skin transforms mbik_pose_globals wrote, without reading them or the skinned
+ * vertices back.  The semantics are Godot 4.3's MeshStorage::mesh_get_aabb(mesh, skeleton) -- one box
+ * per bone, built when the surface is created (RenderingServer::_surface_set_data), moved by the
+ * skeleton's skin transforms and merged -- and the plane half of AABB::intersects_convex_shape,
+ * restated here; the _cpu entries are the specification and the device gives the same bits.  All
+ * arithmetic is float32, unfused, in the order written.  A box is 6 floats: position x, y, z, then
+ * size x, y, z (Godot's AABB).
+ *
+ * 1. Bone boxes, computed by mbik_mesh_create and mbik_mesh_create_shaped from the arrays they
+ * validate (no further failure case: a call that succeeded before ABI 14 still does):
+ *   for v ascending, for k = 0 .. influences-1:
+ *     w = weights[v][k]; b = bone_indices[v][k]; p = positions[v]
+ *     if (w == 0) continue                          +0 and -0 are skipped; NaN and negative weights count
+ *     if bone b is not yet used: box[b] = { p, (1e-5f, 1e-5f, 1e-5f) }; used[b] = 1
+ *     else (AABB::expand_to): begin = box[b].position; end = box[b].position + box[b].size
+ *                             per axis: if (p < begin) begin = p; if (p > end) end = p
+ *                             box[b] = { begin, end - begin }
+ * A NaN coordinate fails both compares, so it changes nothing after the first hit; as a first hit
+ * it is stored as given.  An unused bone has used = 0 and a box of six zeros (Godot marks it with
+ * size (-1,-1,-1); the flag is the same information without a magic value).  Blend shapes do not
+ * enter the boxes -- Godot's behaviour, and the reason it has extra_cull_margin; `margin` of
+ * mbik_cull_boxes is the remedy.  The mesh keeps the used bones' boxes on its device in a table of
+ * its own.  mbik_mesh_bone_boxes copies the boxes out: boxes [bone_count][6], used [bone_count],
+ * host memory.  mbik_bone_boxes_cpu is the host-only form with mbik_mesh_create's checks (any bone
+ * count); MBIK_EINVAL also for a null boxes or used with bone_count > 0. */
+int32_t mbik_mesh_bone_boxes(const mbik_mesh *mesh, float *boxes, uint8_t *used);
+int32_t mbik_bone_boxes_cpu(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
+		const int32_t *bone_indices, const float *weights, float *boxes, uint8_t *used);
+/* 2. One box per skeleton.  For skeleton s, over the used bones j in ascending order:
+ *   t = xform_aabb(skin[s][j], box[j])              Transform3D::xform(AABB):
+ *         mn = box.position; mx = box.position + box.size
+ *         for row i: lo = hi = origin[i]
+ *           for column c = 0..2: e = basis[i][c] * mn[c]; f = basis[i][c] * mx[c]
+ *                                if (e < f) { lo += e; hi += f } else { lo += f; hi += e }
+ *         t = { lo, hi - lo }
+ *   first used bone: acc = t
+ *   otherwise (AABB::merge_with): e1 = acc.size + acc.position; e2 = t.size + t.position
+ *         per axis: mn = acc.position < t.position ? acc.position : t.position
+ *                   mx = e1 > e2 ? e1 : e2
+ *         acc = { mn, mx - mn }
+ * and boxes[s] = acc.  A mesh without a used bone (or without vertices) writes six zeros; Godot
+ * falls back to the surface's static box there (a stated deviation).  Non-finite values go where
+ * those compares send them (no fminf / fmaxf).  The merge is a chain, not a reduction: every step
+ * re-derives the end from the rounded size, so the bits are those of the ascending order and of no
+ * other.  Device buffers on the mesh's device, asynchronous on hip_stream (NULL = default stream):
+ *   skin   [count][bones][12], e.g. mbik_pose_globals' output with inv_bind on the same stream
+ *   boxes  [count][6]
+ * MBIK_EINVAL: a null mesh, count < 0, a null skin or boxes, boxes overlapping skin.  count == 0
+ * returns MBIK_OK without a launch.  Buffers need float alignment only; element offsets are 64-bit.
+ * mbik_skin_bounds_cpu is the host-only form: bone_boxes [bone_count][6] and used [bone_count] as
+ * mbik_mesh_bone_boxes gives them, any bone count. */
+int32_t mbik_skin_bounds(mbik_mesh *mesh, int32_t count, const float *skin, float *boxes, void *hip_stream);
+int32_t mbik_skin_bounds_cpu(int32_t bone_count, const float *bone_boxes, const uint8_t *used, int32_t count, const float *skin,
+		float *boxes);
+/* 3. The plane test and the ordered visible list.  For skeleton s, in this order:
+ *   (p, z) = boxes[s]
+ *   if skeleton_global: (p, z) = xform_aabb(skeleton_global[s], p, z)     to world space, as in 2.
+ *   if (margin != 0): p = p - margin; z = z + margin * 2.0f               Godot's extra_cull_margin
+ *   e = p + z
+ *   for each plane i ascending (normal n, distance d; the normal points out of the frustum):
+ *     c = (n.x > 0 ? p.x : e.x, n.y > 0 ? p.y : e.y, n.z > 0 ? p.z : e.z)   the corner with the least n.x
+ *     if (((n.x*c.x + n.y*c.y) + n.z*c.z) > d): culled, stop                Plane::is_point_over
+ *   otherwise visible
+ * A box that touches a plane (the dot product equals d) is visible.  A NaN anywhere fails the
+ * compare, so such a skeleton stays visible: the conservative side.  plane_count == 0 makes every
+ * skeleton visible.  Device buffers on the mesh's device except `planes`:
+ *   boxes           [count][6], e.g. mbik_skin_bounds' output on the same stream
+ *   skeleton_global [count][12] basis rows, then origin, as in mbik_capture_targets, or NULL
+ *   planes          HOST [plane_count][4]: normal x, y, z, then d; copied at the call into the
+ *                   kernels' arguments, so the call stays asynchronous and the array may be reused at once
+ *   visible         [count] bytes, 0 or 1, or NULL
+ *   indices         [count], or NULL: indices[0 .. n) are the visible s in ascending order (the same
+ *                   list on every run); indices[n ..] is not touched
+ *   visible_count   [1]: n, written by every call (the caller does not clear it); required with
+ *                   indices, optional without
+ * Asynchronous on hip_stream.  The mesh gives the device and owns the scratch for the per-block
+ * counts behind the list, so calls on one mesh are stream-ordered (use one stream per mesh, or order
+ * the streams); the scratch grows with the largest count seen, and growing it waits for the device.
+ * MBIK_EINVAL: a null mesh, null boxes with count > 0, count < 0, plane_count outside
+ * [0, MBIK_CULL_MAX_PLANES], null planes with plane_count > 0, visible and indices both NULL, indices
+ * without visible_count, an output overlapping an input or another output.  count == 0 writes
+ * visible_count[0] = 0 when given and launches nothing else.  mbik_cull_boxes_cpu is the same on
+ * host buffers, without a mesh. */
+#define MBIK_CULL_MAX_PLANES 16
+int32_t mbik_cull_boxes(mbik_mesh *mesh, int32_t count, const float *boxes, const float *skeleton_global, float margin,
+		int32_t plane_count, const float *planes, uint8_t *visible, int32_t *indices, int32_t *visible_count, void *hip_stream);
+int32_t mbik_cull_boxes_cpu(int32_t count, const float *boxes, const float *skeleton_global, float margin, int32_t plane_count,
+		const float *planes, uint8_t *visible, int32_t *indices, int32_t *visible_count);
 
 /* Heterogeneous batches: several plans (distinct rigs, e.g. a crowd of different characters)
  * solved by ONE launch, each plan with its own layout.  The reference runs one

@@ -163,6 +163,21 @@ struct mbik_plan {
 #endif
 };
 
+// One mesh surface on one device (host_skin.cpp creates it; host_bounds.cpp reads its bone boxes).
+struct mbik_mesh {
+	int device = 0, cu_count = 256;
+	int32_t B = 0, V = 0, K = 4;
+	bool normals = false;
+	int32_t P = 0, mode = 0;         // shapes (P == 0: a mesh without)
+	mbik_host::DevBuf mesh;          // skin_layout()'s planes, then morph_layout()'s
+	// the bone boxes (bounds.h): host copies for mbik_mesh_bone_boxes, and the used bones' records on the device
+	std::vector<float> bone_boxes;   // [B][6]
+	std::vector<uint8_t> bone_used;  // [B]
+	int32_t used_bones = 0;
+	mbik_host::DevBuf bone_table;    // [used_bones] 32-byte records (bone_table_pack)
+	mbik_host::DevBuf cull_totals;   // mbik_cull_boxes' block counts; grows with the largest count seen
+};
+
 namespace mbik_host {
 
 // MBIK_OK, or MBIK_ENODEV "no HIP device visible" / MBIK_EINVAL with `out_of_range`.
@@ -174,6 +189,9 @@ inline bool overlap(const void *a, size_t na, const void *b, size_t nb) {
 	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
 	return x < y + nb && y < x + na;
 }
+
+// The mesh checks mbik_mesh_create and the _cpu entries share (skin.h's skin_check_mesh with its error text; host_skin.cpp).
+int check_mesh(int32_t B, int32_t V, int32_t K, const float *positions, const int32_t *bone_indices, const float *weights);
 
 // device-memory areas addressed through buffer resources (32-bit byte offsets): the state of
 // placements 1 and 2, and the setup tables of every layout that can (kTab32 / kTabTiled)

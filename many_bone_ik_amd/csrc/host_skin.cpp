@@ -3,21 +3,30 @@
 // mbik_skin_vertices_cpu, which runs the same per-vertex code (skin.h) on the host.  The
 // semantics are those of Godot's skeleton compute shader on ArrayMesh surface arrays;
 // DESIGN.md §14.  Blend shapes in front of the skinning (ABI 13, morph.h):
-// mbik_mesh_create_shaped, mbik_skin_vertices_shaped and mbik_skin_vertices_shaped_cpu.
+// mbik_mesh_create_shaped, mbik_skin_vertices_shaped and mbik_skin_vertices_shaped_cpu.  The mesh
+// also carries its bone boxes (ABI 14, bounds.h); host_bounds.cpp uses them.
 #include "host.h"
 
+#include "bounds.h"
 #include "morph.h"
 #include "skin.h"
 
 using namespace mbik_host;
 
-struct mbik_mesh {
-	int device = 0, cu_count = 256;
-	int32_t B = 0, V = 0, K = 4;
-	bool normals = false;
-	int32_t P = 0, mode = 0;         // shapes (P == 0: a mesh without)
-	DevBuf mesh;                     // skin_layout()'s planes, then morph_layout()'s
-};
+namespace mbik_host {
+
+int check_mesh(int32_t B, int32_t V, int32_t K, const float *positions, const int32_t *bone_indices, const float *weights) {
+	int64_t bad_v = 0;
+	int bad_k = 0;
+	const mbik::SkinCheck c = mbik::skin_check_mesh(B, V, K, positions, bone_indices, weights, &bad_v, &bad_k);
+	if (c == mbik::SKIN_BAD_INDEX)
+		return fail(MBIK_EINVAL, "vertex " + std::to_string(bad_v) + " influence " + std::to_string(bad_k) + ": bone index " +
+				std::to_string(bone_indices[bad_v * K + bad_k]) + " outside [0, " + std::to_string(B) + ")");
+	if (c != mbik::SKIN_OK) return fail(MBIK_EINVAL, mbik::skin_check_text(c));
+	return MBIK_OK;
+}
+
+} // namespace mbik_host
 
 namespace {
 
@@ -54,17 +63,6 @@ SkinShape shape_of(const mbik_mesh *m, int64_t count, bool shaped) {
 	const int lanes = std::min<int64_t>(sh.chunk, m->V);
 	sh.vshift = lanes <= 64 ? 6 : (lanes <= 128 ? 7 : 8);
 	return sh;
-}
-
-int check_mesh(int32_t B, int32_t V, int32_t K, const float *positions, const int32_t *bone_indices, const float *weights) {
-	int64_t bad_v = 0;
-	int bad_k = 0;
-	const mbik::SkinCheck c = mbik::skin_check_mesh(B, V, K, positions, bone_indices, weights, &bad_v, &bad_k);
-	if (c == mbik::SKIN_BAD_INDEX)
-		return fail(MBIK_EINVAL, "vertex " + std::to_string(bad_v) + " influence " + std::to_string(bad_k) + ": bone index " +
-				std::to_string(bone_indices[bad_v * K + bad_k]) + " outside [0, " + std::to_string(B) + ")");
-	if (c != mbik::SKIN_OK) return fail(MBIK_EINVAL, mbik::skin_check_text(c));
-	return MBIK_OK;
 }
 
 // The argument checks of a skinning call past the mesh's own; 0 = launch, 1 = nothing to do.
@@ -134,6 +132,17 @@ int create_mesh(int32_t bone_count, int32_t vertex_count, int32_t influences, co
 		if (int rc = m->mesh.reserve(packed.size(), "hipMalloc failed for the mesh")) return rc;
 		if (hipMemcpy(m->mesh.as<void>(), packed.data(), packed.size(), hipMemcpyHostToDevice) != hipSuccess)
 			return fail(MBIK_EHIP, "hipMemcpy failed for the mesh");
+	}
+	// the bone boxes (bounds.h): a table of their own, the used bones only
+	m->bone_boxes.resize((size_t)bone_count * 6), m->bone_used.resize((size_t)bone_count);
+	mbik::bone_boxes_build(bone_count, vertex_count, influences, positions, bone_indices, weights, m->bone_boxes.data(), m->bone_used.data());
+	m->used_bones = mbik::bone_table_count(bone_count, m->bone_used.data());
+	if (m->used_bones > 0) {
+		std::vector<unsigned char> table((size_t)m->used_bones * mbik::kBoneRecordBytes);
+		mbik::bone_table_pack(bone_count, m->bone_boxes.data(), m->bone_used.data(), table.data());
+		if (int rc = m->bone_table.reserve(table.size(), "hipMalloc failed for the mesh's bone boxes")) return rc;
+		if (hipMemcpy(m->bone_table.as<void>(), table.data(), table.size(), hipMemcpyHostToDevice) != hipSuccess)
+			return fail(MBIK_EHIP, "hipMemcpy failed for the mesh's bone boxes");
 	}
 	*out_mesh = m.release();
 	return MBIK_OK;

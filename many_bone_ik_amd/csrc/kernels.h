@@ -173,6 +173,17 @@ hipError_t launch_skin(hipStream_t st, int K, int count, int B, int V, int S, in
 // is device memory [count][P]; mode is a MorphMode.
 hipError_t launch_skin_shaped(hipStream_t st, int K, int mode, int count, int B, int V, int P, int S, int chunk, int chunks, int vshift,
 		const unsigned char *mesh, bool mesh_normals, const float *skin, const float *shape_weights, float *out_p, float *out_n);
+// k_bounds.hip: mbik_skin_bounds (bounds.h).  Grid = ceil(count / S) blocks of S skeletons, S * max(B, 1) * 48 bytes of LDS a
+// block (the matrices; the transformed boxes overwrite them); table is the device copy of the U used bones' records
+// (bone_table_pack), U may be 0.
+hipError_t launch_skin_bounds(hipStream_t st, int count, int B, int U, int S, const unsigned char *table, const float *skin,
+		float *boxes);
+// k_bounds.hip: mbik_cull_boxes (bounds.h).  One thread per skeleton, 256 a block; planes is host memory, copied into the
+// kernels' arguments; totals is device scratch of cull_blocks(count) ints, needed when indices or visible_count is given.
+// Up to three launches in stream order: verdicts and block counts, the scan of the counts, the placement of the indices.
+constexpr int cull_blocks(int count) { return (int)(((int64_t)count + 255) / 256); }
+hipError_t launch_cull(hipStream_t st, int count, const float *boxes, const float *skeleton_global, float margin, int plane_count,
+		const float *planes, uint8_t *visible, int32_t *indices, int32_t *visible_count, int32_t *totals);
 // k_blend.hip: mbik_pose_blend (blend.h).  One thread per bone of the total_bones = count * B, 256 bones a block, 20 KiB
 // of static LDS; influence_per_skeleton (device, [count]) overrides influence when given; pose_out may be pose_in or pose_mod.
 hipError_t launch_blend(hipStream_t st, int64_t total_bones, int B, int libm, float influence, const float *influence_per_skeleton,

@@ -11,6 +11,12 @@ Blend shapes (ABI 13): a `Mesh` created with `shape_positions` c
 shared by every skeleton, `Mesh.skin(..., shape_weights_ptr=...)` morphs each skeleton by its own P
 weights in front of the skinning (mbik_skin_vertices_shaped), `skin_vertices_cpu(...,
 shape_weights=...)` is the host side and `synthetic_shapes()` the seeded generator.
+
+Bounds and culling (ABI 14): a `Mesh` carries one box per bone (`Mesh.bone_boxes()`),
+`Mesh.bounds()` merges them, moved by each skeleton's skin transforms, into one box per skeleton
+(mbik_skin_bounds), and `Mesh.cull()` tests those boxes against frustum planes and writes the
+verdicts and the ascending list of visible skeletons (mbik_cull_boxes), all on the device.
+`bone_boxes_cpu()`, `skin_bounds_cpu()` and `cull_boxes_cpu()` are the host sides.
 """
 from __future__ import annotations
 
@@ -92,6 +98,31 @@ class Mesh:
         check(self._L.mbik_skin_vertices(self.h, count, C.c_void_p(skin_ptr or None), C.c_void_p(out_positions_ptr or None),
                                          C.c_void_p(out_normals_ptr or None), C.c_void_p(stream or None)))
 
+    def bone_boxes(self):
+        """mbik_mesh_bone_boxes: (boxes [bones][6] position then size, used [bones] uint8); an unused
+        bone's box is six zeros."""
+        boxes = np.zeros((self.bone_count, 6), np.float32)
+        used = np.zeros((self.bone_count,), np.uint8)
+        check(self._L.mbik_mesh_bone_boxes(self.h, _ptr(boxes), _ptr(used)))
+        return boxes, used
+
+    def bounds(self, skin_ptr: int, boxes_ptr: int, count: int, stream: int = 0) -> None:
+        """mbik_skin_bounds: boxes [count][6] from the device skin transforms [count][bones][12];
+        asynchronous on `stream`."""
+        check(self._L.mbik_skin_bounds(self.h, count, C.c_void_p(skin_ptr or None), C.c_void_p(boxes_ptr or None),
+                                       C.c_void_p(stream or None)))
+
+    def cull(self, boxes_ptr: int, count: int, planes, skeleton_global_ptr: int = 0, margin: float = 0.0, visible_ptr: int = 0,
+             indices_ptr: int = 0, visible_count_ptr: int = 0, stream: int = 0) -> None:
+        """mbik_cull_boxes: the device boxes [count][6] (moved by skeleton_global [count][12] and grown
+        by `margin` when given) against `planes`, a host array [n][4] of outward normals and distances.
+        visible [count] uint8, indices [count] int32 (the visible skeletons, ascending) and
+        visible_count [1] int32 are device pointers; asynchronous on `stream`."""
+        pl = np.ascontiguousarray(planes, np.float32).reshape(-1, 4)
+        check(self._L.mbik_cull_boxes(self.h, count, C.c_void_p(boxes_ptr or None), C.c_void_p(skeleton_global_ptr or None), margin,
+                                      pl.shape[0], _ptr(pl) if pl.shape[0] else None, C.c_void_p(visible_ptr or None),
+                                      C.c_void_p(indices_ptr or None), C.c_void_p(visible_count_ptr or None), C.c_void_p(stream or None)))
+
     def launch_shape(self, count: int) -> tuple[int, int]:
         """(skeletons per block, vertex chunks) of a skin() call for `count` skeletons; of the shaped
         call when the mesh has shapes."""
@@ -143,6 +174,47 @@ def skin_vertices_cpu(bone_count: int, positions, bone_indices, weights, skin, n
     check(L.mbik_skin_vertices_cpu(bone_count, V, idx.shape[1], _ptr(pos), _ptr(nrm), _ptr(idx), _ptr(wgt), count, _ptr(sk),
                                    _ptr(out_p), _ptr(out_n)))
     return out_p, out_n
+
+
+def bone_boxes_cpu(bone_count: int, positions, bone_indices, weights):
+    """mbik_bone_boxes_cpu (host only): (boxes [bones][6], used [bones] uint8) of a mesh."""
+    L = _lib.load()
+    pos, idx, wgt, _ = _mesh_arrays(positions, bone_indices, weights, None)
+    boxes = np.zeros((bone_count, 6), np.float32)
+    used = np.zeros((bone_count,), np.uint8)
+    check(L.mbik_bone_boxes_cpu(bone_count, pos.shape[0], idx.shape[1], _ptr(pos), _ptr(idx), _ptr(wgt), _ptr(boxes), _ptr(used)))
+    return boxes, used
+
+
+def skin_bounds_cpu(bone_boxes, used, skin):
+    """mbik_skin_bounds_cpu (host only): `skin` [count][bones][12] -> boxes [count][6]."""
+    L = _lib.load()
+    bb = np.ascontiguousarray(bone_boxes, np.float32)
+    us = np.ascontiguousarray(used, np.uint8)
+    sk = np.ascontiguousarray(skin, np.float32)
+    B, count = us.shape[0], sk.shape[0]
+    assert bb.shape == (B, 6) and sk.shape == (count, B, 12), (bb.shape, sk.shape)
+    out = np.empty((count, 6), np.float32)
+    check(L.mbik_skin_bounds_cpu(B, _ptr(bb), _ptr(us), count, _ptr(sk), _ptr(out)))
+    return out
+
+
+def cull_boxes_cpu(boxes, planes, skeleton_global=None, margin: float = 0.0):
+    """mbik_cull_boxes_cpu (host only): boxes [count][6] against planes [n][4] ->
+    (visible [count] uint8, indices [visible count] int32 ascending)."""
+    L = _lib.load()
+    bx = np.ascontiguousarray(boxes, np.float32)
+    pl = np.ascontiguousarray(planes, np.float32).reshape(-1, 4)
+    sg = None if skeleton_global is None else np.ascontiguousarray(skeleton_global, np.float32)
+    count = bx.shape[0]
+    assert bx.shape == (count, 6) and (sg is None or sg.shape == (count, 12)), bx.shape
+    visible = np.zeros((count,), np.uint8)
+    indices = np.full((count,), -1, np.int32)
+    n = np.full((1,), -1, np.int32)
+    check(L.mbik_cull_boxes_cpu(count, _ptr(bx), _ptr(sg), margin, pl.shape[0], _ptr(pl) if pl.shape[0] else None, _ptr(visible),
+                                _ptr(indices), _ptr(n)))
+    assert (indices[n[0]:] == -1).all()
+    return visible, indices[:n[0]].copy()
 
 
 def synthetic_mesh(parents, rest_globals, vertex_count: int, influences: int, seed: int):
