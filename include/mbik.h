@@ -768,6 +768,16 @@ int32_t mbik_segment_solve(mbik_plan *plan, int32_t segment, int32_t first, int3
 /* Segment table: for each segment, its root bone, tip bone and parent segment (-1). */
 int32_t mbik_plan_segment_table(const mbik_plan *plan, int32_t *root_bone, int32_t *tip_bone, int32_t *parent_segment,
 		int32_t capacity);
+/* Row-uniform bone-step classes of the plan's current schedule (diagnostics and tests): row_steps
+ * receives each schedule row's bone-step count (row_capacity entries), classes the class id of
+ * every (row, step) in row order (class_capacity entries): 0 where the row's roles take the
+ * general bone-step, else the specialised shape every one of them has there.  Derived from the
+ * schedule, never stored in a plan file.  Returns the row count.  mbik_describe_step_classes is
+ * the host-only form (no device needed) for `desc` at lanes_per_skeleton lanes (0 = automatic). */
+int32_t mbik_plan_step_classes(const mbik_plan *plan, int32_t *row_steps, int32_t row_capacity, int32_t *classes,
+		int32_t class_capacity);
+int32_t mbik_describe_step_classes(const mbik_skeleton_desc *desc, const mbik_config *config, int32_t lanes_per_skeleton,
+		int32_t *row_steps, int32_t row_capacity, int32_t *classes, int32_t class_capacity);
 
 /* Host-only (no device needed): runs the _bone_list_changed segmentation for `desc` and
  * reports the solve order.  bone_list receives ManyBoneIK3D::bone_list (capacity

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "mbik_plan_set_locals_placement", "mbik_plan_set_waves_per_simd", "mbik_plan_set_helper_wave", "mbik_plan_set_wave_roles", "mbik_plan_set_table_addressing", "mbik_plan_rebuild_setup", "mbik_plan_setup_tables",
     "mbik_plan_status", "mbik_plan_debug_helper",
     "mbik_solve", "mbik_solve_checked", "mbik_solve_host", "mbik_segment_solve", "mbik_plan_segment_table", "mbik_describe_topology",
+    "mbik_plan_step_classes", "mbik_describe_step_classes",
     "mbik_group_create", "mbik_group_solve", "mbik_group_destroy", "mbik_multi_create", "mbik_multi_solve",
     "mbik_multi_skeletons", "mbik_multi_destroy", "mbik_capture_targets", "mbik_pose_globals", "mbik_pose_globals_cpu", "mbik_pose_blend", "mbik_pose_blend_cpu", "mbik_clipset_create", "mbik_clipset_destroy", "mbik_clip_sample", "mbik_clip_sample_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
     "mbik_skin_vertices", "mbik_skin_vertices_cpu", "mbik_mesh_launch_shape", "mbik_mesh_create_shaped", "mbik_skin_vertices_shaped",
@@ -206,6 +207,11 @@ def load():
     L.mbik_plan_segment_table.restype = C.c_int32
     L.mbik_describe_topology.argtypes = [C.POINTER(MbikSkeletonDesc), C.POINTER(MbikConfig), vp, vp, vp, vp, vp, vp]
     L.mbik_describe_topology.restype = C.c_int32
+    if hasattr(L, "mbik_plan_step_classes"):  # (absent from older A/B builds)
+        L.mbik_plan_step_classes.argtypes = [vp, vp, C.c_int32, vp, C.c_int32]
+        L.mbik_plan_step_classes.restype = C.c_int32
+        L.mbik_describe_step_classes.argtypes = [C.POINTER(MbikSkeletonDesc), C.POINTER(MbikConfig), C.c_int32, vp, C.c_int32, vp, C.c_int32]
+        L.mbik_describe_step_classes.restype = C.c_int32
     L.mbik_group_create.argtypes = [C.POINTER(vp), C.c_int32, C.POINTER(vp)]
     L.mbik_group_create.restype = C.c_int32
     L.mbik_group_solve.argtypes = [vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]

@@ -317,10 +317,32 @@ __device__ __forceinline__ void qcp_accumulate(QSums &S, const V3 wc1, const V3 
 // the exchange area xw (coop_walk); this wave, the group's first, consumes them, and with hrec
 // its parent-side values come from the group's second wave's record (rw_record): it reads the
 // whole record first and posts hseq in the group's counter hfl (rw_wait).
-template <bool STAB, bool PR, int TA, bool HELP, bool XS, int PM, bool SEL, bool XW, class LV, class GV, class FP, class IP>
+// SH: the step's shape.  StepDyn: every topology test at run time.  StepFix<c>: class c of the
+// schedule's row-uniform step classes (plan.h StepClassShape, DevPlan::step_class) -- every role
+// of the wave answers the tests of the step's flag set, of its segment's heading path and of its
+// cone count as the shape says, so they are compile-time constants here and the divergent
+// branches around them (a compare, s_and_saveexec, s_cbranch_execz each) are gone.  The
+// arithmetic is the same text either way.
+struct StepDyn {
+	static constexpr int cls = 0;
+};
+template <int CLS>
+struct StepFix {
+	static constexpr int cls = CLS;
+};
+template <bool STAB, bool PR, int TA, bool HELP, bool XS, int PM, bool SEL, bool XW, class SH = StepDyn, class LV, class GV, class FP, class IP>
 __device__ void bone_step(const DevPlan &t, int seg, int k, int j, int m, int xs, size_t s, const LV &L, const GV &G, const FP TG,
 		const FP ST, const IP SF, const FP HS, const FP OE, const FP MS, double &prev_dev, const EffPre &pre, bool hoist,
 		const float4 *hrec, int *hfl, int hseq, bool *hstuck, const float *xw MBIK_PROF_PARAM) {
+	constexpr bool FIX = SH::cls != 0;
+	static_assert(!FIX || (!STAB && !XS && !XW), "step classes: the one-wave builds without stabilization");
+	constexpr mbik::StepClassShape shape = mbik::step_class_shape(SH::cls);
+	if constexpr (FIX) {
+		// one hoisted effector solved by one lane: the segment's heading path
+		m = 1;
+		xs = 0;
+		hoist = true;
+	}
 	MBIK_PROF_T(pt0);
 #ifdef MBIK_PROF
 	uint64_t pt1 = pt0, pt3 = pt0;
@@ -329,7 +351,8 @@ __device__ void bone_step(const DevPlan &t, int seg, int k, int j, int m, int xs
 	// the step's topology, resolved on the host (HostPlan::step_rec): no dependent lookups
 	const int4 sr = t.step_rec[k];
 	const int b = sr.x & 0xffff;
-	const int flags = sr.z & 0xffff;           // bone_flags | SR_* bits
+	// bone_flags | SR_* bits (a class fixes its kStepClassFlags)
+	const int flags = FIX ? ((sr.z & 0xffff & ~mbik::kStepClassFlags) | shape.flags) : (sr.z & 0xffff);
 	const int d0 = sr.z >> 16;                 // path index of b's first descendant
 	const int slot = (sr.y >> 16) - 1;         // constraint slot
 	const bool hasP = (flags & mbik::SR_HAS_POSE_PARENT) != 0;
@@ -378,9 +401,9 @@ __device__ void bone_step(const DevPlan &t, int seg, int k, int j, int m, int xs
 		Gb = hasP ? P * Lb : Lb;
 		sto = slerp_to(Gb.b);
 	}
-	const bool translate = (t.seg_flags[seg] & mbik::SF_TRANSLATE) != 0;
-	const int e0 = t.seg_eff_off[seg], e1 = t.seg_eff_off[seg + 1];
-	const int nh = t.seg_nh[seg];
+	const bool translate = !FIX && (t.seg_flags[seg] & mbik::SF_TRANSLATE) != 0;
+	const int e0 = t.seg_eff_off[seg], e1 = FIX ? e0 + 1 : t.seg_eff_off[seg + 1];
+	const int nh = FIX ? 2 : t.seg_nh[seg]; // (a class: two or more headings, only compared below)
 	MBIK_PROF_T(ph0);
 	MBIK_PROF_ADD(8, pt0, ph0);
 	const double *hw = t.seg_hw + t.seg_hw_off[seg];
@@ -868,7 +891,7 @@ __device__ void bone_step(const DevPlan &t, int seg, int k, int j, int m, int xs
 		V3 bdx = xform(Gbd_stale, v3(0.0f, 1.0f, 0.0f));
 		V3 tip = xform(X3{Pinv, xform(Pinv, -Gco.o)}, bdx); // Gco.basis == P.basis
 		double in_bounds = 1.0;
-		V3 inl = local_point_in_limits<TA, SEL>(t, slot, s, tip, in_bounds);
+		V3 inl = local_point_in_limits<TA, SEL, FIX ? shape.ncones : -1>(t, slot, s, tip, in_bounds);
 		if (in_bounds < 0) {
 			V3 p2 = xform(Gco, inl);
 			Q rect = arc<SEL>(bdx - Gco.o, p2 - Gco.o);

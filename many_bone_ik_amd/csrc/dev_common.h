@@ -723,9 +723,10 @@ __device__ __forceinline__ V3 great_tangent_triangle(V3 c1xc2, V3 a1, V3 a2, V3 
 // reading the basis at each step is faster: C3 -1 %, C4 -1.6 %, C5 -3 % (same-box A/B).  The
 // one-wave build keeps the whole per-segment effector data (`hoist` in solve_block).
 // IKKusudama3D::get_local_point_in_limits (ik_kusudama_3d.cpp:273-332)
-template <int TA = kTab64, bool SEL = false>
+// NC: the cone count when the step's class fixes it (StepFix), else -1: read from the table.
+template <int TA = kTab64, bool SEL = false, int NC = -1>
 __device__ V3 local_point_in_limits(const DevPlan &t, int slot, size_t s, V3 in_point, double &in_bounds) {
-	const int nc = t.cons_ncones[slot];
+	const int nc = NC >= 0 ? NC : t.cons_ncones[slot];
 	V3 point = normalized_t<SEL>(in_point);
 	float closest_cos = -2.0f;
 	in_bounds = -1;

@@ -84,6 +84,12 @@ int upload_topology(mbik_plan *p) {
 		const int nq = mbik::row_max_steps(h, (int)(i / (size_t)h.K));
 		rows[i] = make_int4(h.sched[i].seg, h.sched[i].j, h.sched[i].m, h.sched[i].flags | (nq << 8));
 	}
+	// the rows' step classes follow the schedule (HostPlan::step_class; solve_block.h row_classes):
+	// no table pointer of their own, so DevPlan -- every solve kernel's argument -- keeps its size
+	for (size_t i = 0; i < h.step_class.size(); i += 4) {
+		auto w = [&](size_t j) { return j < h.step_class.size() ? h.step_class[j] : 0; };
+		rows.push_back(make_int4(w(i), w(i + 1), w(i + 2), w(i + 3)));
+	}
 	add(rows.data(), rows.size() * sizeof(int4), 4, d.o_sched);
 #define MBIK_ADD(T, name) \
 	if (std::string(#name) != "sched") add(h.name.data(), h.name.size() * sizeof(h.name[0]), sizeof(T) >= 16 ? 4 : (sizeof(T) >= 8 ? 2 : 1), d.o_##name);
@@ -1036,6 +1042,31 @@ int32_t mbik_plan_segment_table(const mbik_plan *p, int32_t *root, int32_t *tip,
 		if (parent) parent[i] = h.seg_parent[i];
 	}
 	return h.NS;
+}
+
+static int32_t step_classes_of(const mbik::HostPlan &h, int32_t *row_steps, int32_t row_cap, int32_t *classes, int32_t class_cap) {
+	int n = 0;
+	for (int r = 0; r < h.nrows; r++) {
+		const int nq = mbik::row_max_steps(h, r);
+		if (row_steps && r < row_cap) row_steps[r] = nq;
+		for (int q = 0; q < nq; q++, n++)
+			if (classes && n < class_cap) classes[n] = mbik::step_class_at(h, r, q);
+	}
+	return h.nrows;
+}
+int32_t mbik_plan_step_classes(const mbik_plan *p, int32_t *row_steps, int32_t row_cap, int32_t *classes, int32_t class_cap) {
+	if (!p) return fail(MBIK_EINVAL, "null plan");
+	return step_classes_of(p->host, row_steps, row_cap, classes, class_cap);
+}
+int32_t mbik_describe_step_classes(const mbik_skeleton_desc *desc, const mbik_config *config, int32_t lanes_per_skeleton,
+		int32_t *row_steps, int32_t row_cap, int32_t *classes, int32_t class_cap) {
+	if (!desc || !config) return fail(MBIK_EINVAL, "null argument");
+	mbik::HostPlan h;
+	std::string err = mbik::build_topology(*desc, *config, h);
+	if (!err.empty()) return fail(MBIK_EINVAL, err);
+	h.N = 1;
+	mbik::build_schedule(h, std::max(0, lanes_per_skeleton), 1);
+	return step_classes_of(h, row_steps, row_cap, classes, class_cap);
 }
 
 int32_t mbik_solve_host(mbik_plan *p, int32_t first, int32_t count, const float *pose_in, const float *targets, float *pose_out) {

@@ -575,6 +575,7 @@ int64_t topology_bytes(const HostPlan &p) {
 	ints(4 * p.seg_bones.size() + 3); // step_rec, 16-byte aligned
 	ints(p.seg_effs.size() + 1);      // seg_eff_lcp
 	ints(p.seg_effs.size() + 1);      // seg_eff_grp
+	ints(p.step_class.size() + 3);    // behind the schedule's rows, in whole int4s
 	return (w + 4) * 4;
 }
 
@@ -640,6 +641,56 @@ static bool cm_split_groups(HostPlan &p, int sg, int m) {
 	const int T = p.eff_path[p.eff_path_off[p.seg_effs[e0]] + L - 1];
 	p.seg_eff_grp[e0] |= (T + 1) << 4;
 	return true;
+}
+
+// The class of bone-step q of one task (step_class_shape's test of one role): the step's flag
+// set, its segment's heading path and its cone count against the shape's.
+static bool step_matches(const HostPlan &p, const SchedTask &tk, int q, int cls) {
+	const int sg = tk.seg, k = p.seg_bone_off[sg] + q;
+	const int b = p.seg_bones[k], pp = p.bone_pose_parent[b];
+	const int flags = (p.bone_flags[b] & (BF_ORIENT | BF_AXIAL | BF_PINNED)) | (pp != POSE_PARENT_NONE ? SR_HAS_POSE_PARENT : 0) |
+			(pp >= 0 ? SR_PARENT_GLOBAL : 0);
+	const StepClassShape sh = step_class_shape(cls);
+	if (flags != sh.flags) return false;
+	// one effector, hoisted, solved by one lane from registers with several headings; no translation
+	if (p.seg_eff_off[sg + 1] - p.seg_eff_off[sg] != 1 || tk.m != 1 || p.seg_nh[sg] < 2) return false;
+	if ((p.seg_flags[sg] & (SF_TRANSLATE | SF_STAB)) || (tk.flags & (SCHED_XS | SCHED_CMSPLIT))) return false;
+	const int slot = p.bone_cons[b];
+	return slot >= 0 && p.cons_ncones[slot] == sh.ncones;
+}
+
+// HostPlan::step_class: per schedule row and step index, the class every role with a step there
+// belongs to, else 0.
+static void classify_steps(HostPlan &p) {
+	std::vector<uint8_t> cls;
+	std::vector<int32_t> off(p.nrows);
+	for (int r = 0; r < p.nrows; r++) {
+		while (cls.size() % 4) cls.push_back(0);
+		off[r] = p.nrows + (int32_t)(cls.size() / 4);
+		const int nq = row_max_steps(p, r);
+		for (int q = 0; q < nq; q++) {
+			int c = 0;
+			for (int cand = 1; cand <= kStepClasses && !c; cand++) {
+				bool all = true, any = false;
+				for (int l = 0; l < p.K && all; l++) {
+					const SchedTask &tk = p.sched[(size_t)r * p.K + l];
+					if (tk.seg < 0 || q >= p.seg_bone_off[tk.seg + 1] - p.seg_bone_off[tk.seg]) continue; // no step here
+					any = true;
+					all = step_matches(p, tk, q, cand);
+				}
+				if (all && any) c = cand;
+			}
+			cls.push_back((uint8_t)c);
+		}
+	}
+	while (cls.size() % 4) cls.push_back(0);
+	p.step_class.assign(off.begin(), off.end());
+	for (size_t i = 0; i < cls.size(); i += 4)
+		p.step_class.push_back((int32_t)((uint32_t)cls[i] | (uint32_t)cls[i + 1] << 8 | (uint32_t)cls[i + 2] << 16 | (uint32_t)cls[i + 3] << 24));
+}
+
+int step_class_at(const HostPlan &p, int row, int q) {
+	return (p.step_class[p.step_class[row] + (q >> 2)] >> (8 * (q & 3))) & 0xff;
 }
 
 void build_schedule(HostPlan &p, int32_t lanes, int64_t nlaunch, int32_t spw_override, int32_t interval_override,
@@ -841,6 +892,7 @@ void build_schedule(HostPlan &p, int32_t lanes, int64_t nlaunch, int32_t spw_ove
 	// MI355X: interval 2 ~1.5 %, no interior checkpoints 6-8 %; mbik_plan_autotune measures
 	// instead of modelling).  Residency comes from the runtime's occupancy query (LDS
 	// allocation granularity and the register budget: at most one wave per SIMD).
+	classify_steps(p);
 	const int64_t topo = topology_bytes(p);
 	const int64_t kCUs = cus;
 	auto set_interval = [&](int c) -> double {

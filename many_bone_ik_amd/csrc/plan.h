@@ -32,6 +32,26 @@ enum SegFlags : int32_t {
 	                   // child segments get 0, ik_bone_segment_3d.cpp:398)
 };
 
+// Row-uniform bone-step classes (HostPlan::step_class).  The roles of a schedule row read their
+// step's topology per lane, so every test of it is a divergent branch although the roles of most
+// rows answer alike.  Where every role that has a step at (row, step index) matches one of the
+// shapes below, the one-wave kernels run a bone_step instantiation with the shape's answers
+// compiled in (bone_step.h StepFix); class 0 takes the run-time tests.  A shape fixes the step's
+// flag set (kStepClassFlags of the step record's flags), its cone count and its segment's heading
+// path: one effector, hoisted, solved by one lane from registers with two or more headings, no
+// translation, no stabilization, no split exchange.  The child-effector count stays a run-time
+// value (one loop test; fixing it would send the step above each chain's tip to class 0).
+//   1  parented by a checkpointed global, swing and twist limits, two cones, not pinned
+//   2  the same, pinned (a chain's tip)
+struct StepClassShape {
+	int32_t flags, ncones;
+};
+constexpr int kStepClasses = 2;
+constexpr int32_t kStepClassFlags = BF_ORIENT | BF_AXIAL | BF_PINNED | SR_HAS_POSE_PARENT | SR_PARENT_GLOBAL;
+constexpr StepClassShape step_class_shape(int cls) {
+	return StepClassShape{BF_ORIENT | BF_AXIAL | SR_HAS_POSE_PARENT | SR_PARENT_GLOBAL | (cls == 2 ? (int32_t)BF_PINNED : 0), 2};
+}
+
 // Pose-node parent codes (IKNode3D parent of godot_skeleton_aligned_transform).
 constexpr int32_t POSE_PARENT_NONE = -1;      // released ik_origin (earlier roots of a multi-root skeleton)
 constexpr int32_t POSE_PARENT_ORIGIN = -2;    // the live ik_origin (identity)
@@ -174,6 +194,10 @@ struct HostPlan {
 	// the parent's global or of its checkpoint, + 1) | (constraint slot + 1) << 16; z = bone
 	// flags | SR_* bits | path start (depth + 1) << 16; w = child-effector offset | count << 16.
 	std::vector<int32_t> step_rec;
+	// Row-uniform step classes (StepClassShape), derived from the schedule: [nrows] word offsets
+	// into this table, then per row its steps' class ids, one byte each, four a word
+	// (step_class_at).  Not part of a plan file: build_schedule rebuilds it.
+	std::vector<int32_t> step_class;
 	// Per seg_effs index i: how many leading bones effector seg_effs[i]'s path (from the root)
 	// shares with the previous effector's of the same segment (0 for a segment's first), plus
 	// a trailing 0.  The solve reuses the previous effector's walk down to that depth.
@@ -251,5 +275,7 @@ int64_t rw_record_bytes(const HostPlan &plan);
 int64_t rw_extra_lds_bytes(const HostPlan &plan);
 // The longest segment of schedule row `row`, in bone-steps.
 int row_max_steps(const HostPlan &plan, int row);
+// The class of bone-step q of schedule row `row` (HostPlan::step_class); 0 = none.
+int step_class_at(const HostPlan &plan, int row, int q);
 
 } // namespace mbik

@@ -41,6 +41,17 @@ __device__ __forceinline__ int row_steps(const DevPlan &t, int r, int seg_lo, in
 	}
 	return __builtin_amdgcn_readfirstlane(n);
 }
+// The class of bone-step q of schedule row r (DevPlan::step_class, plan.h StepClassShape): a
+// wave-uniform value, so the dispatch on it is a scalar branch.  0: the general bone_step.
+// (A sub-range solve masks roles; the roles left still match a class that held for all of them.)
+// The table follows the schedule's rows in the topology blob (upload_topology).
+__device__ __forceinline__ const int *row_classes(const DevPlan &t, int r) {
+	const int *tab = reinterpret_cast<const int *>(t.sched + t.nrows * t.K);
+	return tab + __builtin_amdgcn_readfirstlane(tab[r]);
+}
+__device__ __forceinline__ int step_class_of(const int *rcls, int q) {
+	return __builtin_amdgcn_readfirstlane((rcls[q >> 2] >> (8 * (q & 3))) & 0xff);
+}
 
 // RW (wave roles, HostPlan::wave_roles): the block is RW waves; lane = skeleton (64 per block),
 // wave = the schedule's role, so every topology value a wave reads is uniform over it.
@@ -244,6 +255,7 @@ __device__ __forceinline__ void solve_block(DevPlan &t, int blk, int first, int 
 				EffPre pre;
 				const bool hoist = act && t.seg_eff_off[seg + 1] - e0 == 1 && (task.z == 1 || t.seg_nh[seg] == 1);
 				if (hoist) load_eff<kTab32>(t, t.seg_effs[e0], TG, s, t.seg_hw + t.seg_hw_off[seg] + t.seg_eff_hoff[e0], pre);
+				const int *rcls = row_classes(t, r);
 				for (int q = 0; q < nq; q++, seq++) {
 					MBIK_PROF_T(hw0);
 					bool b_ready;
@@ -257,9 +269,17 @@ __device__ __forceinline__ void solve_block(DevPlan &t, int blk, int first, int 
 #ifdef MBIK_REPLAY
 					if (rp) hrec = rp + (size_t)seq * kHelpF4 * 64;
 #endif
-					if (k0 + q < k1)
-						bone_step<false, true, kTab32, true, false, PM, true, false>(t, seg, k0 + q, task.y, task.z, task.w & mbik::SCHED_XS, s, L, G, TG,
-								ST, SF, HS, OE, MS, prev_dev, pre, hoist, hrec, b_ready ? nullptr : hfl, seq, &stuck, nullptr MBIK_PROF_ARG);
+					auto step = [&](auto shape) __attribute__((always_inline)) {
+						if (k0 + q < k1)
+							bone_step<false, true, kTab32, true, false, PM, true, false, decltype(shape)>(t, seg, k0 + q, task.y, task.z,
+									task.w & mbik::SCHED_XS, s, L, G, TG, ST, SF, HS, OE, MS, prev_dev, pre, hoist, hrec, b_ready ? nullptr : hfl, seq,
+									&stuck, nullptr MBIK_PROF_ARG);
+					};
+					switch (step_class_of(rcls, q)) {
+					case 1: step(StepFix<1>{}); break;
+					case 2: step(StepFix<2>{}); break;
+					default: step(StepDyn{});
+					}
 					help_post(hfl + 2, seq + 1);
 					slot = slot + 1 == kHelpSlots ? 0 : slot + 1;
 				}
@@ -364,7 +384,12 @@ __device__ __forceinline__ void solve_block(DevPlan &t, int blk, int first, int 
 			double prev_dev = INFINITY;
 			EffPre pre;
 			bool hoist = false;
-			for (;;) {
+			// A single row: every role's segment starts at the first trip, so trip q runs bone-step q
+			// of each role that still has one, and the row's step classes apply (the one-wave
+			// placement-0 build without stabilization; a packed level's lanes are at different steps).
+			constexpr bool kClasses = !STAB && PL == 0 && HOIST && T32 && !XS && RW == 0;
+			const int *rcls = kClasses && r1 == r + 1 ? row_classes(t, r) : nullptr;
+			for (int q = 0;; q++) {
 				while (k >= ke && rr + 1 < r1) {
 					task = t.sched[++rr * K + role];
 					if (valid && task.x >= seg_lo && task.x <= seg_hi) {
@@ -382,8 +407,22 @@ __device__ __forceinline__ void solve_block(DevPlan &t, int blk, int first, int 
 					}
 				}
 				if (k >= ke) break;
-				bone_step<STAB, HOIST || PL == 2, TA, false, XS, PM, HOIST, false>(t, seg, k, task.y, task.z, task.w & mbik::SCHED_XS, s, L, G, TG,
-						ST, SF, HS, OE, MS, prev_dev, pre, hoist, nullptr, nullptr, 0, nullptr, nullptr MBIK_PROF_ARG);
+				if constexpr (kClasses) {
+					auto step = [&](auto shape) __attribute__((always_inline)) {
+						bone_step<STAB, HOIST || PL == 2, TA, false, XS, PM, HOIST, false, decltype(shape)>(t, seg, k, task.y, task.z,
+								task.w & mbik::SCHED_XS, s, L, G, TG, ST, SF, HS, OE, MS, prev_dev, pre, hoist, nullptr, nullptr, 0, nullptr,
+								nullptr MBIK_PROF_ARG);
+					};
+					switch (rcls ? step_class_of(rcls, q) : 0) {
+					case 1: step(StepFix<1>{}); break;
+					case 2: step(StepFix<2>{}); break;
+					default: step(StepDyn{});
+					}
+				} else {
+					// (the other builds keep the plain call: their register allocation is at its cap)
+					bone_step<STAB, HOIST || PL == 2, TA, false, XS, PM, HOIST, false>(t, seg, k, task.y, task.z, task.w & mbik::SCHED_XS, s, L, G, TG,
+							ST, SF, HS, OE, MS, prev_dev, pre, hoist, nullptr, nullptr, 0, nullptr, nullptr MBIK_PROF_ARG);
+				}
 				k++;
 			}
 			__syncthreads();

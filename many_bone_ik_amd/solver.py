@@ -73,6 +73,26 @@ def describe_topology(parents, pins, constraints=(), *, iterations=15, default_d
     return dict(bone_list=bl[:nbl.value], seg_root=r[:ns], seg_tip=t[:ns], seg_parent=p[:ns], seg_headings=nh[:ns])
 
 
+def _step_classes(call) -> list:
+    """Per schedule row the class id of each of its bone-steps (call = the C accessor, partly applied)."""
+    rows = check(call(None, 0, None, 0))
+    steps = np.zeros(max(1, rows), np.int32)
+    check(call(_ptr(steps), rows, None, 0))
+    cls = np.zeros(max(1, int(steps[:rows].sum())), np.int32)
+    check(call(_ptr(steps), rows, _ptr(cls), cls.shape[0]))
+    off = np.concatenate([[0], np.cumsum(steps[:rows])])
+    return [cls[off[r]:off[r + 1]].copy() for r in range(rows)]
+
+
+def describe_step_classes(parents, pins, constraints=(), *, lanes=0, iterations=15, default_damp=math.radians(5.0)) -> list:
+    """Host-only (mbik_describe_step_classes): the row-uniform bone-step classes of the schedule at `lanes` lanes."""
+    L = _lib.load()
+    constraints = list(constraints)
+    mc = max([1] + [int(c.get("cone_count", 0)) for c in constraints])
+    d = _Desc(parents, pins, constraints, mc, iterations, default_damp, False, 0, None)
+    return _step_classes(lambda rs, rc, cs, cc: L.mbik_describe_step_classes(C.byref(d.desc), C.byref(d.cfg), int(lanes), rs, rc, cs, cc))
+
+
 def pose_globals_cpu(parents, pins, pose, inv_bind=None, targets=None):
     """mbik_pose_globals_cpu (host only): skeleton-space bone transforms of `pose` [n][bones][10]
     -- Skeleton3D::get_bone_global_pose for every bone, times inv_bind [bones][12] when given --
@@ -385,6 +405,10 @@ class Plan:
         r = np.zeros(n, np.int32); t = np.zeros(n, np.int32); p = np.zeros(n, np.int32)
         check(self._L.mbik_plan_segment_table(self.h, _ptr(r), _ptr(t), _ptr(p), n))
         return r, t, p
+
+    def step_classes(self):
+        """mbik_plan_step_classes: per schedule row the class id of each of its bone-steps."""
+        return _step_classes(lambda rs, rc, cs, cc: self._L.mbik_plan_step_classes(self.h, rs, rc, cs, cc))
 
     def close(self):
         if getattr(self, "h", None):

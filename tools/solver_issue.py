@@ -46,6 +46,7 @@ out = {
     "helper_issue_frac": 4.0 * (block_valu - solver_valu) / wave_cycles,
     "solver_lds_insts_per_wave": round(r1["SQ_INSTS_LDS"] / blocks, 1),
     "solver_salu_insts_per_wave": round(r1["SQ_INSTS_SALU"] / blocks, 1),
+    "solver_branch_insts_per_wave": round(r2["SQ_INSTS_BRANCH"] / r2["SQ_WAVES"], 1),
     "solver_valu_classes_per_wave": {name[len("SQ_INSTS_VALU_"):]: round(r2[name] / r2["SQ_WAVES"], 1)
                                      for name in r2 if name.startswith("SQ_INSTS_VALU_")},
     "replay_wave_cycles": round(4.0 * r1["SQ_WAVE_CYCLES"] / r1["SQ_WAVES"], 1),

@@ -265,6 +265,80 @@ __global__ __launch_bounds__(64) void kern(float *out, double *outd, long long *
 	if (threadIdx.x == 0) cyc[blockIdx.x] = t1 - t0;
 }
 
+// What a branch costs a lone wave (one wave per block; with 4 * CUs blocks one wave per SIMD, as
+// the solve kernels run): s_memtime around a dependent v_add_f32 chain of BR_REPS * BR_ADDS adds,
+//   FORM 0  plain;
+//   FORM 1  every N adds the compiler's divergent-if: v_cmp (true in every lane), s_and_saveexec,
+//           s_cbranch_execz (never taken), the body (the group's last add), s_or exec;
+//   FORM 2  every N adds a taken scalar branch (s_cmp, s_cbranch_scc1) over one cache line of s_nop;
+//   FORM 3  FORM 1 without its s_cbranch_execz (the mask bookkeeping alone).
+#define BR_REPS 32
+#define BR_ADDS 512
+#define BR_STR2(x) #x
+#define BR_STR(x) BR_STR2(x)
+template <int FORM, int N>
+__global__ __launch_bounds__(64) void branch_kern(float *out, long long *cyc, float seed, int zero) {
+	float a = seed + threadIdx.x * 1e-3f;
+	const float b = 1e-3f;
+	const long long t0 = __builtin_amdgcn_s_memtime();
+#pragma unroll 1
+	for (int i = 0; i < BR_REPS; i++) {
+		if constexpr (FORM == 0) {
+			asm volatile(".rept " BR_STR(BR_ADDS) "\n v_add_f32 %0, %0, %1\n.endr" : "+v"(a) : "v"(b));
+		} else if constexpr (FORM == 1) {
+			asm volatile(".rept %c2\n"
+					" .rept %c3\n v_add_f32 %0, %0, %1\n .endr\n"
+					" v_cmp_o_f32 vcc, %0, %0\n s_and_saveexec_b64 s[40:41], vcc\n s_cbranch_execz 1f\n"
+					" v_add_f32 %0, %0, %1\n"
+					"1: s_or_b64 exec, exec, s[40:41]\n"
+					".endr"
+					: "+v"(a) : "v"(b), "n"(BR_ADDS / N), "n"(N - 1) : "vcc", "scc", "s40", "s41");
+		} else if constexpr (FORM == 2) {
+			asm volatile(".rept %c3\n"
+					" .rept %c4\n v_add_f32 %0, %0, %1\n .endr\n"
+					" s_cmp_eq_u32 %2, 0\n s_cbranch_scc1 1f\n"
+					" .rept 16\n s_nop 0\n .endr\n"
+					"1:\n"
+					".endr"
+					: "+v"(a) : "v"(b), "s"(zero), "n"(BR_ADDS / N), "n"(N) : "scc");
+		} else {
+			asm volatile(".rept %c2\n"
+					" .rept %c3\n v_add_f32 %0, %0, %1\n .endr\n"
+					" v_cmp_o_f32 vcc, %0, %0\n s_and_saveexec_b64 s[40:41], vcc\n"
+					" v_add_f32 %0, %0, %1\n"
+					" s_or_b64 exec, exec, s[40:41]\n"
+					".endr"
+					: "+v"(a) : "v"(b), "n"(BR_ADDS / N), "n"(N - 1) : "vcc", "scc", "s40", "s41");
+		}
+	}
+	asm volatile("" :: "v"(a));
+	const long long t1 = __builtin_amdgcn_s_memtime();
+	out[blockIdx.x * 64 + threadIdx.x] = a;
+	if (threadIdx.x == 0) cyc[blockIdx.x] = t1 - t0;
+}
+template <int FORM, int N>
+double run_branch(float *o, long long *c, long long *h, int blocks) {
+	for (int rep = 0; rep < 2; rep++) {
+		hipLaunchKernelGGL((branch_kern<FORM, N>), dim3(blocks), dim3(64), 0, 0, o, c, 1.25f, 0);
+		hipDeviceSynchronize();
+	}
+	hipMemcpy(h, c, blocks * sizeof(long long), hipMemcpyDeviceToHost);
+	double s = 0;
+	for (int i = 0; i < blocks; i++) s += (double)h[i];
+	return s / blocks;
+}
+// cycles per not-taken saveexec / execz pair, per taken scalar branch and per mask pair without
+// its branch, at one branch every N adds
+template <int N>
+void branch_report(float *o, long long *c, long long *h, int blocks) {
+	const double plain = run_branch<0, N>(o, c, h, blocks), pair = run_branch<1, N>(o, c, h, blocks),
+			taken = run_branch<2, N>(o, c, h, blocks), mask = run_branch<3, N>(o, c, h, blocks);
+	const double adds = (double)BR_REPS * BR_ADDS, sites = adds / N;
+	printf("{\"op\": \"branch\", \"waves_per_cu\": %d, \"adds_per_branch\": %d, \"cycles_per_add\": %.2f, "
+			"\"cycles_per_execz_pair\": %.2f, \"cycles_per_taken_branch\": %.2f, \"cycles_per_mask_pair_no_branch\": %.2f}\n",
+			blocks / 256, N, plain / adds, (pair - plain) / sites, (taken - plain) / sites, (mask - plain) / sites);
+}
+
 template <int OP>
 double run(float *o, double *od, long long *c, long long *h, int blocks) {
 	hipLaunchKernelGGL(kern<OP>, dim3(blocks), dim3(64), 0, 0, o, od, c, 1.25f);
@@ -288,8 +362,8 @@ int main() {
 			"ds_read_b32 chase", "sqrt_f64(+add) dep", "cvt+add_f64+cvt dep", "mul+add f32 dep", "pk_mul_f32 indep2 (per pk op)", "mul_f32 indep4", "pk_add_f32 indep2 (per pk op)", "B3*B3 dep", "B3*B3 quad-coop dep", "orthonormalize dep", "normalize V3 dep", "normalize V3 quad-coop dep", "X3*X3 dep", "div_rcp64 dep", "normalize rcp64 dep", "mul_f64 indep4",
 			"cvt f32-f64-f32 dep", "mul_f32 dep", "div_f32 same-divisor indep4", "add_f64 dep", "add_f64 indep4",
 			"div_exact64 dep", "normalize exact64 dep", "sin_poly64(+add) dep", "gd_sqrt(+add) dep", "B3*B3 packed-xy dep"};
-	double per[] = {16, 16, 16, 16, 16, 16, 16, 16, 16, 4, 4, 16, 16, 16, 8, 16, 16, 16, 4, 4, 4, 16, 16, 4, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16};
-	double r[36];
+	double per[] = {16, 16, 16, 16, 16, 16, 16, 16, 16, 4, 4, 16, 16, 16, 8, 16, 16, 16, 4, 4, 4, 16, 16, 4, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 4};
+	double r[37];
 	r[0] = run<0>(o, od, c, h, blocks); r[1] = run<1>(o, od, c, h, blocks); r[2] = run<2>(o, od, c, h, blocks);
 	r[3] = run<3>(o, od, c, h, blocks); r[4] = run<4>(o, od, c, h, blocks); r[5] = run<5>(o, od, c, h, blocks);
 	r[6] = run<6>(o, od, c, h, blocks); r[7] = run<7>(o, od, c, h, blocks); r[8] = run<8>(o, od, c, h, blocks);
@@ -305,5 +379,15 @@ int main() {
 	r[35] = run<35>(o, od, c, h, blocks); r[36] = run<36>(o, od, c, h, blocks);
 	for (int i = 0; i < 37; i++)
 		printf("{\"op\": \"%s\", \"cycles_per_op\": %.2f}\n", names[i], r[i] / (REPS * per[i]));
+	// the cost of a branch to a lone wave: one wave per CU, then one per SIMD (256 CUs)
+	static long long hb[1024];
+	float *ob; long long *cb;
+	hipMalloc(&ob, 1024 * 64 * sizeof(float));
+	hipMalloc(&cb, 1024 * sizeof(long long));
+	for (int nb = 256; nb <= 1024; nb *= 4) {
+		branch_report<8>(ob, cb, hb, nb);
+		branch_report<16>(ob, cb, hb, nb);
+		branch_report<32>(ob, cb, hb, nb);
+	}
 	return 0;
 }
