@@ -57,7 +57,7 @@ extern "C" {
 #define MBIK_EUNSUPPORTED (-4)
 #define MBIK_ENODEV (-5)
 
-#define MBIK_ABI_VERSION 14
+#define MBIK_ABI_VERSION 15
 
 typedef struct mbik_plan mbik_plan;
 typedef struct mbik_group mbik_group;
@@ -705,6 +705,50 @@ int32_t mbik_cull_boxes(mbik_mesh *mesh, int32_t count, const float *boxes, cons
 		int32_t plane_count, const float *planes, uint8_t *visible, int32_t *indices, int32_t *visible_count, void *hip_stream);
 int32_t mbik_cull_boxes_cpu(int32_t count, const float *boxes, const float *skeleton_global, float margin, int32_t plane_count,
 		const float *planes, uint8_t *visible, int32_t *indices, int32_t *visible_count);
+
+/* List-driven skinning (ABI 15): the skeletons a device-resident list names -- mbik_cull_boxes'
+ * indices and visible_count on the same stream are such a list -- skinned without a host read-back
+ * of the list or its length.  mbik_skin_vertices_listed_cpu is the specification and the device gives
+ * the same bits:
+ *   n = min(max(list_count[0], 0), max_list)       list_count is read on the device, never by the host
+ *   for r = 0 .. n-1:  s = indices[r]
+ *     if (s < 0 || s >= count) continue             the entry is skipped: nothing is read or written for it
+ *     row = (flags & MBIK_SKIN_LIST_COMPACT) ? r : s
+ *     out_positions[row][v], out_normals[row][v], all v  =  what mbik_skin_vertices (shape_weights NULL) or
+ *         mbik_skin_vertices_shaped (shape_weights given) writes to row s for skin[s] (and shape_weights[s]),
+ *         bit for bit
+ *   every other row of the outputs is not touched
+ * Device buffers on the mesh's device, asynchronous on hip_stream (NULL = default stream):
+ *   indices       [max_list]; need not be ascending or unique.  A duplicate writes the same bits twice
+ *                 in place and one row each when compact; entries at and past n are not read
+ *   list_count    [1]: the list's length
+ *   max_list      HOST: an upper bound on the length, which sizes the launch; it may exceed count
+ *   skin          [count][bones][12], as for mbik_skin_vertices
+ *   shape_weights [count][shape_count], or NULL: a NULL on a shaped mesh skins the base arrays, as
+ *                 mbik_skin_vertices does
+ *   out_positions, out_normals (or NULL)
+ *                 in place [count][vertices][3]; compact [max_list][vertices][3], row r belonging to
+ *                 skeleton indices[r], so the caller's instance map is the list itself
+ * The mesh's own bone indices are checked once by the host when the mesh is created; this list is
+ * device data the host never sees, so here the kernel tests every entry against [0, count) itself.
+ * MBIK_EINVAL: everything mbik_skin_vertices or mbik_skin_vertices_shaped refuses (a null mesh,
+ * count < 0, a null skin or out_positions, out_normals for a mesh without normals, an output that
+ * overlaps skin, shape_weights or the other output), a negative max_list, unknown flag bits, a
+ * non-null shape_weights on a mesh without shapes, null indices or list_count with work to do, an
+ * output overlapping indices or list_count; output sizes follow the flag.  count == 0, max_list == 0
+ * or a mesh without vertices returns MBIK_OK without a launch.  Buffers need float alignment only;
+ * element offsets are 64-bit.  The launch shape is mbik_mesh_launch_shape's for max_list skeletons
+ * (of the plain call when shape_weights is NULL): a block owns that many consecutive list entries.
+ * The _cpu form takes mbik_skin_vertices_shaped_cpu's mesh arguments (any bone and shape count);
+ * `shapes` may be NULL for a mesh without shapes, and every buffer is host memory. */
+#define MBIK_SKIN_LIST_COMPACT 1u
+int32_t mbik_skin_vertices_listed(mbik_mesh *mesh, int32_t count, const int32_t *indices, const int32_t *list_count,
+		int32_t max_list, const float *skin, const float *shape_weights, uint32_t flags, float *out_positions,
+		float *out_normals, void *hip_stream);
+int32_t mbik_skin_vertices_listed_cpu(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
+		const float *normals, const int32_t *bone_indices, const float *weights, const mbik_mesh_shapes *shapes, int32_t count,
+		const int32_t *indices, const int32_t *list_count, int32_t max_list, const float *skin, const float *shape_weights,
+		uint32_t flags, float *out_positions, float *out_normals);
 
 /* Heterogeneous batches: several plans (distinct rigs, e.g. a crowd of different characters)
  * solved by ONE launch, each plan with its own layout.  The reference runs one

@@ -5,11 +5,14 @@
 // DESIGN.md §14.  Blend shapes in front of the skinning (ABI 13, morph.h):
 // mbik_mesh_create_shaped, mbik_skin_vertices_shaped and mbik_skin_vertices_shaped_cpu.  The mesh
 // also carries its bone boxes (ABI 14, bounds.h); host_bounds.cpp uses them.
+// List-driven skinning (ABI 15, skin_list.h): mbik_skin_vertices_listed, which launches
+// k_skin_list.hip's kernels, and mbik_skin_vertices_listed_cpu.
 #include "host.h"
 
 #include "bounds.h"
 #include "morph.h"
 #include "skin.h"
+#include "skin_list.h"
 
 using namespace mbik_host;
 
@@ -66,14 +69,15 @@ SkinShape shape_of(const mbik_mesh *m, int64_t count, bool shaped) {
 }
 
 // The argument checks of a skinning call past the mesh's own; 0 = launch, 1 = nothing to do.
+// out_rows: the outputs' rows where they are not `count` (the listed call's compact form; 0 = nothing to do).
 int check_call(int32_t B, int32_t V, bool mesh_normals, int32_t count, const float *skin, const float *out_positions,
-		const float *out_normals) {
+		const float *out_normals, int64_t out_rows = -1) {
 	if (count < 0) return fail(MBIK_EINVAL, "negative count");
 	if (out_normals && !mesh_normals) return fail(MBIK_EINVAL, "out_normals given for a mesh without normals");
-	if (count == 0 || V == 0) return 1;
+	if (count == 0 || V == 0 || out_rows == 0) return 1;
 	if (!skin) return fail(MBIK_EINVAL, "null skin");
 	if (!out_positions) return fail(MBIK_EINVAL, "null out_positions");
-	const size_t nskin = (size_t)count * B * 12 * sizeof(float), nout = (size_t)count * V * 3 * sizeof(float);
+	const size_t nskin = (size_t)count * B * 12 * sizeof(float), nout = (size_t)(out_rows < 0 ? count : out_rows) * V * 3 * sizeof(float);
 	if (overlap(skin, nskin, out_positions, nout)) return fail(MBIK_EINVAL, "out_positions overlaps skin");
 	if (out_normals && overlap(skin, nskin, out_normals, nout)) return fail(MBIK_EINVAL, "out_normals overlaps skin");
 	if (out_normals && overlap(out_positions, nout, out_normals, nout)) return fail(MBIK_EINVAL, "out_normals overlaps out_positions");
@@ -92,14 +96,39 @@ int check_shapes(int32_t B, int32_t V, bool mesh_normals, const mbik_mesh_shapes
 	return MBIK_OK;
 }
 
-// The checks of a shaped call's weights, past check_call's.
+// The checks of a shaped call's weights, past check_call's; out_rows as there.
 int check_shape_weights(int32_t V, int32_t P, int32_t count, const float *shape_weights, const float *out_positions,
-		const float *out_normals) {
+		const float *out_normals, int64_t out_rows = -1) {
 	if (!shape_weights) return fail(MBIK_EINVAL, "null shape_weights");
-	const size_t nw = (size_t)count * P * sizeof(float), nout = (size_t)count * V * 3 * sizeof(float);
+	const size_t nw = (size_t)count * P * sizeof(float), nout = (size_t)(out_rows < 0 ? count : out_rows) * V * 3 * sizeof(float);
 	if (overlap(shape_weights, nw, out_positions, nout)) return fail(MBIK_EINVAL, "out_positions overlaps shape_weights");
 	if (out_normals && overlap(shape_weights, nw, out_normals, nout)) return fail(MBIK_EINVAL, "out_normals overlaps shape_weights");
 	return MBIK_OK;
+}
+
+// The checks of a listed call (mbik_skin_vertices_listed and its _cpu form) past the mesh's and the shapes' own: everything
+// the plain or the shaped call refuses, with the outputs sized by the flag, and the list's own.  P: the mesh's shapes
+// (0: none).  0 = run, 1 = nothing to do.
+int check_listed(int32_t B, int32_t V, bool mesh_normals, int32_t P, int32_t count, const int32_t *indices, const int32_t *list_count,
+		int32_t max_list, const float *skin, const float *shape_weights, uint32_t flags, const float *out_positions,
+		const float *out_normals) {
+	if (flags & ~mbik::kSkinListFlags) return fail(MBIK_EINVAL, "unknown flag bits");
+	if (max_list < 0) return fail(MBIK_EINVAL, "negative max_list");
+	if (shape_weights && P < 1) return fail(MBIK_EINVAL, "shape_weights given for a mesh without shapes");
+	const int64_t rows = max_list == 0 ? 0 : ((flags & mbik::kSkinListCompact) ? max_list : count);
+	if (int rc = check_call(B, V, mesh_normals, count, skin, out_positions, out_normals, rows)) return rc;
+	if (shape_weights)
+		if (int rc = check_shape_weights(V, P, count, shape_weights, out_positions, out_normals, rows)) return rc;
+	if (!indices) return fail(MBIK_EINVAL, "null indices");
+	if (!list_count) return fail(MBIK_EINVAL, "null list_count");
+	const size_t nout = (size_t)rows * V * 3 * sizeof(float), nidx = (size_t)max_list * sizeof(int32_t);
+	for (const float *out : {out_positions, out_normals}) {
+		if (!out) continue;
+		const char *which = out == out_positions ? "out_positions" : "out_normals";
+		if (overlap(indices, nidx, out, nout)) return fail(MBIK_EINVAL, std::string(which) + " overlaps indices");
+		if (overlap(list_count, sizeof(int32_t), out, nout)) return fail(MBIK_EINVAL, std::string(which) + " overlaps list_count");
+	}
+	return 0;
 }
 
 // mbik_mesh_create (shaped == false: `shapes` is not looked at) and mbik_mesh_create_shaped
@@ -202,6 +231,21 @@ int32_t mbik_skin_vertices_shaped(mbik_mesh *m, int32_t count, const float *skin
 	return MBIK_OK;
 }
 
+int32_t mbik_skin_vertices_listed(mbik_mesh *m, int32_t count, const int32_t *indices, const int32_t *list_count, int32_t max_list,
+		const float *skin, const float *shape_weights, uint32_t flags, float *out_positions, float *out_normals, void *hip_stream) {
+	if (!m) return fail(MBIK_EINVAL, "null mesh");
+	const int rc = check_listed(m->B, m->V, m->normals, m->P, count, indices, list_count, max_list, skin, shape_weights, flags,
+			out_positions, out_normals);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	DeviceGuard guard(m->device);
+	const SkinShape sh = shape_of(m, max_list, shape_weights != nullptr); // (a tile is S list entries)
+	hipError_t e = mbik::launch_skin_listed(reinterpret_cast<hipStream_t>(hip_stream), m->K, m->mode, count, m->B, m->V, m->P, sh.S,
+			sh.chunk, sh.chunks, sh.vshift, m->mesh.as<unsigned char>(), m->normals, skin, shape_weights, indices, list_count, max_list,
+			(flags & mbik::kSkinListCompact) != 0, out_positions, out_normals);
+	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("listed skinning launch failed: ") + hipGetErrorString(e));
+	return MBIK_OK;
+}
+
 int32_t mbik_skin_vertices_cpu(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
 		const float *normals, const int32_t *bone_indices, const float *weights, int32_t count, const float *skin,
 		float *out_positions, float *out_normals) {
@@ -223,6 +267,23 @@ int32_t mbik_skin_vertices_shaped_cpu(int32_t bone_count, int32_t vertex_count, 
 	if (int rw = check_shape_weights(vertex_count, shapes->shape_count, count, shape_weights, out_positions, out_normals)) return rw;
 	mbik::morph_skin_vertices_host(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, shapes->shape_count,
 			shapes->mode, shapes->positions, shapes->normals, count, skin, shape_weights, out_positions, out_normals);
+	return MBIK_OK;
+}
+
+int32_t mbik_skin_vertices_listed_cpu(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
+		const float *normals, const int32_t *bone_indices, const float *weights, const mbik_mesh_shapes *shapes, int32_t count,
+		const int32_t *indices, const int32_t *list_count, int32_t max_list, const float *skin, const float *shape_weights,
+		uint32_t flags, float *out_positions, float *out_normals) {
+	if (int rc = check_mesh(bone_count, vertex_count, influences, positions, bone_indices, weights)) return rc;
+	if (shapes)
+		if (int rc = check_shapes(bone_count, vertex_count, normals != nullptr, shapes, -1)) return rc;
+	const int32_t P = shapes ? shapes->shape_count : 0;
+	const int rc = check_listed(bone_count, vertex_count, normals != nullptr, P, count, indices, list_count, max_list, skin,
+			shape_weights, flags, out_positions, out_normals);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	mbik::skin_vertices_listed_host(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, P,
+			shapes ? shapes->mode : 0, shapes ? shapes->positions : nullptr, shapes ? shapes->normals : nullptr, count, indices,
+			list_count, max_list, skin, shape_weights, (flags & mbik::kSkinListCompact) != 0, out_positions, out_normals);
 	return MBIK_OK;
 }
 

@@ -173,6 +173,13 @@ hipError_t launch_skin(hipStream_t st, int K, int count, int B, int V, int S, in
 // is device memory [count][P]; mode is a MorphMode.
 hipError_t launch_skin_shaped(hipStream_t st, int K, int mode, int count, int B, int V, int P, int S, int chunk, int chunks, int vshift,
 		const unsigned char *mesh, bool mesh_normals, const float *skin, const float *shape_weights, float *out_p, float *out_n);
+// k_skin_list.hip: mbik_skin_vertices_listed (skin_list.h).  launch_skin's block (shape_weights null) or launch_skin_shaped's,
+// with the same LDS; grid = ceil(max_list / S) tiles of list entries x `chunks` vertex chunks, S <= 64 and max_list >= 1.  indices
+// (device, [max_list]) and list_count (device, [1]) are read by the kernel only, which tests every entry against [0, count);
+// compact: entry r writes output row r, otherwise row indices[r].
+hipError_t launch_skin_listed(hipStream_t st, int K, int mode, int count, int B, int V, int P, int S, int chunk, int chunks, int vshift,
+		const unsigned char *mesh, bool mesh_normals, const float *skin, const float *shape_weights, const int32_t *indices,
+		const int32_t *list_count, int max_list, bool compact, float *out_p, float *out_n);
 // k_bounds.hip: mbik_skin_bounds (bounds.h).  Grid = ceil(count / S) blocks of S skeletons, S * max(B, 1) * 48 bytes of LDS a
 // block (the matrices; the transformed boxes overwrite them); table is the device copy of the U used bones' records
 // (bone_table_pack), U may be 0.

@@ -17,6 +17,10 @@ Bounds and culling (ABI 14): a `Mesh` carries one box per bone (
 (mbik_skin_bounds), and `Mesh.cull()` tests those boxes against frustum planes and writes the
 verdicts and the ascending list of visible skeletons (mbik_cull_boxes), all on the device.
 `bone_boxes_cpu()`, `skin_bounds_cpu()` and `cull_boxes_cpu()` are the host sides.
+
+List-driven skinning (ABI 15): `Mesh.skin_listed()` skins the skeletons a device list
+names -- `Mesh.cull()`'s indices and visible_count, on the same stream and never read by the host --
+in place or compacted (mbik_skin_vertices_listed); `skin_vertices_listed_cpu()` is the host side.
 """
 from __future__ import annotations
 
@@ -123,6 +127,20 @@ class Mesh:
                                       pl.shape[0], _ptr(pl) if pl.shape[0] else None, C.c_void_p(visible_ptr or None),
                                       C.c_void_p(indices_ptr or None), C.c_void_p(visible_count_ptr or None), C.c_void_p(stream or None)))
 
+    def skin_listed(self, skin_ptr: int, out_positions_ptr: int, count: int, indices_ptr: int, list_count_ptr: int,
+                    max_list: int | None = None, compact: bool = False, out_normals_ptr: int = 0, shape_weights_ptr: int = 0,
+                    stream: int = 0) -> None:
+        """mbik_skin_vertices_listed: skin() for the skeletons the device list indices [max_list] int32
+        names, its length read from list_count [1] int32 on the device (cull()'s indices and
+        visible_count on the same stream are such a list); max_list defaults to `count`.  An entry
+        outside [0, count) is skipped.  In place the outputs are [count][vertices][3] and unlisted rows
+        are not touched; compact they are [max_list][vertices][3] and row r belongs to indices[r]."""
+        check(self._L.mbik_skin_vertices_listed(self.h, count, C.c_void_p(indices_ptr or None), C.c_void_p(list_count_ptr or None),
+                                                count if max_list is None else max_list, C.c_void_p(skin_ptr or None),
+                                                C.c_void_p(shape_weights_ptr or None), _lib.SKIN_LIST_COMPACT if compact else 0,
+                                                C.c_void_p(out_positions_ptr or None), C.c_void_p(out_normals_ptr or None),
+                                                C.c_void_p(stream or None)))
+
     def launch_shape(self, count: int) -> tuple[int, int]:
         """(skeletons per block, vertex chunks) of a skin() call for `count` skeletons; of the shaped
         call when the mesh has shapes."""
@@ -174,6 +192,41 @@ def skin_vertices_cpu(bone_count: int, positions, bone_indices, weights, skin, n
     check(L.mbik_skin_vertices_cpu(bone_count, V, idx.shape[1], _ptr(pos), _ptr(nrm), _ptr(idx), _ptr(wgt), count, _ptr(sk),
                                    _ptr(out_p), _ptr(out_n)))
     return out_p, out_n
+
+
+def skin_vertices_listed_cpu(bone_count: int, positions, bone_indices, weights, skin, indices, list_count, max_list=None,
+                             compact: bool = False, normals=None, shape_positions=None, shape_normals=None,
+                             shape_mode: str = "relative", shape_weights=None, out_positions=None, out_normals=None):
+    """mbik_skin_vertices_listed_cpu (host only): the skeletons indices[0 .. min(max(list_count, 0),
+    max_list)) of `skin` [count][bones][12] -> (positions, normals or None when the mesh has none),
+    [max_list][V][3] when compact and [count][V][3] otherwise.  max_list defaults to len(indices).  Rows
+    the call does not write keep what out_positions / out_normals (float32 arrays of that shape, written
+    in place) held; NaN when they are not given.  shape_weights [count][P] with shape_positions: the
+    shaped bits; shape_positions alone: the base arrays."""
+    L = _lib.load()
+    pos, idx, wgt, nrm = _mesh_arrays(positions, bone_indices, weights, normals)
+    sk = np.ascontiguousarray(skin, np.float32)
+    ind = np.ascontiguousarray(indices, np.int32).reshape(-1)
+    cnt = np.asarray([int(list_count)], np.int32)
+    count, V = sk.shape[0], pos.shape[0]
+    max_list = ind.shape[0] if max_list is None else int(max_list)
+    assert sk.shape == (count, bone_count, 12) and 0 <= max_list <= ind.shape[0], (sk.shape, max_list)
+    rows = max_list if compact else count
+    outs = []
+    for given, wanted in ((out_positions, True), (out_normals, nrm is not None)):
+        if given is None:
+            given = np.full((rows, V, 3), np.nan, np.float32) if wanted else None
+        assert given is None or (given.dtype == np.float32 and given.shape == (rows, V, 3) and given.flags.c_contiguous)
+        outs.append(given)
+    shapes, _keep = _shape_arrays(V, shape_positions, shape_normals, shape_mode)
+    cw = None
+    if shape_weights is not None:
+        cw = np.ascontiguousarray(shape_weights, np.float32)
+        assert shapes is None or cw.shape == (count, shapes.shape_count), cw.shape
+    check(L.mbik_skin_vertices_listed_cpu(bone_count, V, idx.shape[1], _ptr(pos), _ptr(nrm), _ptr(idx), _ptr(wgt),
+                                          None if shapes is None else C.byref(shapes), count, _ptr(ind), _ptr(cnt), max_list, _ptr(sk),
+                                          _ptr(cw), _lib.SKIN_LIST_COMPACT if compact else 0, _ptr(outs[0]), _ptr(outs[1])))
+    return outs[0], outs[1]
 
 
 def bone_boxes_cpu(bone_count: int, positions, bone_indices, weights):
