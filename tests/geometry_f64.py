@@ -11,7 +11,10 @@ Definitions used:
   (cA, rA) and (cB, rB) have radius tr = (pi - rA - rB) / 2 and centres t with
   angle(t, cA) = rA + tr and angle(t, cB) = rB + tr;
 - the path between A and B is, on each side of the A-B great circle, the spherical triangle
-  (A, t, B) minus the open tangent cap around t.
+  (A, t, B) minus the open tangent cap around t;
+- the constraint frames of a Kusudama, its twist limit (swing-twist decomposition about +Y, the
+  twist clamped to half the range either side of the centre) and the one-cone swing snap: the
+  last section of this file.
 
 The limits below are 4 x the worst value measured against the CPU oracle over the fixed seeds of
 tests/test_geometry_cpu.py; DESIGN.md section 7a ("Float64 geometry") holds the table of measured
@@ -239,3 +242,127 @@ def xform_affine_inverse_f64(a):
     org = -(inv @ Ao)
     dorg = (dinv @ np.abs(Ao)) * (1 + _gamma(3)) + _gamma(3) * (np.abs(inv) @ np.abs(Ao))
     return np.concatenate([inv.reshape(-1), org]), np.concatenate([dinv.reshape(-1), dorg])
+
+
+# --- constraint frames and the two snaps of a Kusudama ---------------------
+# Every rotation below is a 3x3 matrix in the constrained bone's parent frame.  L is the bone's local
+# rotation, D its bone-direction frame (a child of the bone's own frame), Y = (0, 1, 0).
+Y_AXIS = np.array([0.0, 1.0, 0.0])
+ARC_DEADBAND = math.acos(1.0 - 1.0e-5)   # 4.47e-3 rad: Godot's Quaternion(v0, v1) is the identity below it
+ARC_DEADBAND_MARGIN = 1.0e-4             # rad: arcs this close to the deadband are not asserted either way
+
+
+def shortest_arc(a, b, deadband=True):
+    """The rotation by angle(a, b) about a x b: it takes a to b along their great circle.  Every arc
+    of the reference is a Godot Quaternion(v0, v1), which returns the identity when the vectors'
+    cosine exceeds 1 - CMP_EPSILON (1e-5): arcs below ARC_DEADBAND are not made (section 7a's quirk
+    table).  deadband=False gives the plain definition."""
+    a, b = unit(a), unit(b)
+    ang = float(angle(a, b))
+    if ang < (ARC_DEADBAND if deadband else 1e-300):
+        return np.eye(3)
+    return axis_angle_matrix(np.cross(a, b), ang)
+
+
+def near_deadband(ang):
+    """True where an arc of this angle could fall on either side of the deadband in float32."""
+    return np.abs(np.asarray(ang) - ARC_DEADBAND) < ARC_DEADBAND_MARGIN
+
+
+def bone_direction_frame(child_positions):
+    """A bone's bone-direction frame from the local positions of its children (unit scales).  The
+    reference turns the frame by the arc from the children's centroid direction to the frame's own
+    +Y (ik_bone_3d.cpp:91: Quaternion(child_centroid, bone_direction), applied on the left), so the
+    frame's +Y ends mirrored through +Y, not on the centroid.  Identity for a childless bone and
+    for a centroid on +Y."""
+    c = np.asarray(child_positions, np.float64).reshape(-1, 3)
+    if len(c) == 0:
+        return np.eye(3)
+    return shortest_arc(c.mean(axis=0), Y_AXIS)
+
+
+def bone_direction_frames(parents, positions, in_list=None):
+    """[bone] frames of one skeleton: positions [B][3] are the rest pose's local positions; a bone's
+    children are its children among the solved bones (`in_list`, default all)."""
+    parents = np.asarray(parents)
+    B = len(parents)
+    in_list = np.ones(B, bool) if in_list is None else np.asarray(in_list, bool)
+    return np.stack([bone_direction_frame([positions[c] for c in range(B) if parents[c] == b and in_list[c]])
+                     for b in range(B)])
+
+
+def twist_direction(cones):
+    """The direction the twist frame's +Y is taken to: the normalised mean of the points half way
+    (along the great circle) between consecutive normalised control points of cones [k][4]; for
+    one cone its control point; None without cones."""
+    cones = np.asarray(cones, np.float64).reshape(-1, 4)
+    if len(cones) == 0:
+        return None
+    c = unit(cones[:, :3])
+    if len(c) == 1:
+        return c[0]
+    return unit(np.mean([unit(c[i] + c[i + 1]) for i in range(len(c) - 1)], axis=0))
+
+
+def twist_frame(cones, reverse_arc=False):
+    """The twist frame in the parent frame: the shortest arc that takes +Y to twist_direction(cones)
+    (ik_kusudama_3d.cpp:37-89); the parent's frame without cones.  reverse_arc (negative control):
+    the arc taken from that direction to +Y."""
+    mean = twist_direction(cones)
+    if mean is None:
+        return np.eye(3)
+    return shortest_arc(mean, Y_AXIS) if reverse_arc else shortest_arc(Y_AXIS, mean)
+
+
+def twist_centre(min_angle, times=2):
+    """+Z turned about +Y by min_angle twice (ik_kusudama_3d.cpp:108-111 applies twist_min_rot to
+    +Z and then to the result), as the rotation about +Y.  times=1 is the negative control."""
+    return axis_angle_matrix(Y_AXIS, times * float(min_angle))
+
+
+def twist_angle(A):
+    """The angle about +Y of the twist factor of A = swing * twist: for the quaternion (x, y, z, w)
+    of A it is 2 atan2(y, w), and A[0,2] - A[2,0] = 4wy, A[0,0] + A[2,2] = 2(w^2 - y^2)."""
+    return math.atan2(A[0, 2] - A[2, 0], A[0, 0] + A[2, 2])
+
+
+def twist_offset(L, frame, centre):
+    """The twist angle of the local rotation L away from the centre of the twist range."""
+    return twist_angle(centre.T @ frame.T @ L)
+
+
+def twist_limit(L, frame, centre, twist_range, half=0.5):
+    """(expected rotation, twist angle before): frame * centre * swing * twist with the twist
+    clamped to +-range/2 (ik_kusudama_3d.cpp:117-132).  half=1.0 is the negative control."""
+    A = centre.T @ frame.T @ L
+    t = twist_angle(A)
+    swing = A @ axis_angle_matrix(Y_AXIS, -t)
+    lim = half * float(twist_range)
+    tc = t if lim >= math.pi else min(max(t, -lim), lim)
+    return frame @ centre @ swing @ axis_angle_matrix(Y_AXIS, tc), t
+
+
+def bone_direction(L, D, origin_offset=None):
+    """The direction the swing limit judges, in the parent frame: L * D * (+Y), seen from the
+    orientation frame's origin.  The ordinary solve keeps that origin on the bone's own
+    (ik_bone_3d.cpp:145-151); constraint_mode never moves it off the parent's, so there the tip
+    point is origin_offset (the bone's local position) + L * D * (+Y)."""
+    tip = L @ D @ Y_AXIS
+    if origin_offset is not None:
+        tip = tip + np.asarray(origin_offset, np.float64)
+    return tip
+
+
+def swing_snap_one_cone(L, D, cone, origin_offset=None, radius_scale=1.0):
+    """(expected rotation, angle of the direction beyond the cap, <= 0 inside).  Outside the cap
+    {p : angle(p, c) <= r}, L is turned in the parent frame by the shortest arc from the
+    direction to the point of the cap's circle on the great circle through c and the direction
+    (ik_kusudama_3d.cpp:347-376, ik_open_cone_3d.cpp:358-381)."""
+    cone = np.asarray(cone, np.float64)
+    c, r = unit(cone[:3]), float(cone[3]) * radius_scale
+    d = bone_direction(L, D, origin_offset)
+    excess = float(angle(d, c)) - r
+    if excess <= 0:
+        return L, excess
+    on_circle = axis_angle_matrix(np.cross(c, unit(d)), r) @ c
+    return shortest_arc(d, on_circle) @ L, excess
