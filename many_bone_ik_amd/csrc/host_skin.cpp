@@ -131,6 +131,22 @@ int check_listed(int32_t B, int32_t V, bool mesh_normals, int32_t P, int32_t cou
 	return 0;
 }
 
+// What the three device entry points do behind their checks: guard the mesh's device, pick the launch shape for
+// `tiled` skeletons or list entries, fill in what the mesh knows of `a` (the caller has set count, the buffers and, listed,
+// the list), launch.  A call with a.shape_weights is a shaped one.  failed: the error text's head.
+int launch_on_mesh(const mbik_mesh *m, void *hip_stream, int64_t tiled, mbik::SkinLaunch a, hipError_t (*launch)(const mbik::SkinLaunch &),
+		const char *failed) {
+	DeviceGuard guard(m->device);
+	const SkinShape sh = shape_of(m, tiled, a.shape_weights != nullptr);
+	a.st = reinterpret_cast<hipStream_t>(hip_stream);
+	a.K = m->K, a.mode = m->mode, a.B = m->B, a.V = m->V, a.P = m->P;
+	a.S = sh.S, a.chunk = sh.chunk, a.chunks = sh.chunks, a.vshift = sh.vshift;
+	a.mesh = m->mesh.as<unsigned char>(), a.mesh_normals = m->normals;
+	const hipError_t e = launch(a);
+	if (e != hipSuccess) return fail(MBIK_EHIP, std::string(failed) + hipGetErrorString(e));
+	return MBIK_OK;
+}
+
 // mbik_mesh_create (shaped == false: `shapes` is not looked at) and mbik_mesh_create_shaped
 int create_mesh(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions, const float *normals,
 		const int32_t *bone_indices, const float *weights, bool shaped, const mbik_mesh_shapes *shapes, int32_t device,
@@ -208,12 +224,9 @@ int32_t mbik_skin_vertices(mbik_mesh *m, int32_t count, const float *skin, float
 	if (!m) return fail(MBIK_EINVAL, "null mesh");
 	const int rc = check_call(m->B, m->V, m->normals, count, skin, out_positions, out_normals);
 	if (rc) return rc < 0 ? rc : MBIK_OK;
-	DeviceGuard guard(m->device);
-	const SkinShape sh = shape_of(m, count, false);
-	hipError_t e = mbik::launch_skin(reinterpret_cast<hipStream_t>(hip_stream), m->K, count, m->B, m->V, sh.S, sh.chunk, sh.chunks,
-			sh.vshift, m->mesh.as<unsigned char>(), m->normals, skin, out_positions, out_normals);
-	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("skinning launch failed: ") + hipGetErrorString(e));
-	return MBIK_OK;
+	mbik::SkinLaunch a{};
+	a.count = count, a.skin = skin, a.out_p = out_positions, a.out_n = out_normals;
+	return launch_on_mesh(m, hip_stream, count, a, mbik::launch_skin, "skinning launch failed: ");
 }
 
 int32_t mbik_skin_vertices_shaped(mbik_mesh *m, int32_t count, const float *skin, const float *shape_weights, float *out_positions,
@@ -223,12 +236,9 @@ int32_t mbik_skin_vertices_shaped(mbik_mesh *m, int32_t count, const float *skin
 	const int rc = check_call(m->B, m->V, m->normals, count, skin, out_positions, out_normals);
 	if (rc) return rc < 0 ? rc : MBIK_OK;
 	if (int rw = check_shape_weights(m->V, m->P, count, shape_weights, out_positions, out_normals)) return rw;
-	DeviceGuard guard(m->device);
-	const SkinShape sh = shape_of(m, count, true);
-	hipError_t e = mbik::launch_skin_shaped(reinterpret_cast<hipStream_t>(hip_stream), m->K, m->mode, count, m->B, m->V, m->P, sh.S,
-			sh.chunk, sh.chunks, sh.vshift, m->mesh.as<unsigned char>(), m->normals, skin, shape_weights, out_positions, out_normals);
-	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("shaped skinning launch failed: ") + hipGetErrorString(e));
-	return MBIK_OK;
+	mbik::SkinLaunch a{};
+	a.count = count, a.skin = skin, a.shape_weights = shape_weights, a.out_p = out_positions, a.out_n = out_normals;
+	return launch_on_mesh(m, hip_stream, count, a, mbik::launch_skin, "shaped skinning launch failed: ");
 }
 
 int32_t mbik_skin_vertices_listed(mbik_mesh *m, int32_t count, const int32_t *indices, const int32_t *list_count, int32_t max_list,
@@ -237,13 +247,10 @@ int32_t mbik_skin_vertices_listed(mbik_mesh *m, int32_t count, const int32_t *in
 	const int rc = check_listed(m->B, m->V, m->normals, m->P, count, indices, list_count, max_list, skin, shape_weights, flags,
 			out_positions, out_normals);
 	if (rc) return rc < 0 ? rc : MBIK_OK;
-	DeviceGuard guard(m->device);
-	const SkinShape sh = shape_of(m, max_list, shape_weights != nullptr); // (a tile is S list entries)
-	hipError_t e = mbik::launch_skin_listed(reinterpret_cast<hipStream_t>(hip_stream), m->K, m->mode, count, m->B, m->V, m->P, sh.S,
-			sh.chunk, sh.chunks, sh.vshift, m->mesh.as<unsigned char>(), m->normals, skin, shape_weights, indices, list_count, max_list,
-			(flags & mbik::kSkinListCompact) != 0, out_positions, out_normals);
-	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("listed skinning launch failed: ") + hipGetErrorString(e));
-	return MBIK_OK;
+	mbik::SkinLaunch a{};
+	a.count = count, a.skin = skin, a.shape_weights = shape_weights, a.out_p = out_positions, a.out_n = out_normals;
+	a.indices = indices, a.list_count = list_count, a.max_list = max_list, a.compact = (flags & mbik::kSkinListCompact) != 0;
+	return launch_on_mesh(m, hip_stream, max_list, a, mbik::launch_skin_listed, "listed skinning launch failed: "); // (a tile is S list entries)
 }
 
 int32_t mbik_skin_vertices_cpu(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,

@@ -163,23 +163,31 @@ hipError_t launch_tile_rows(hipStream_t st, const double *src, double *dst, int 
 // [B] (bone, parent) pairs in schedule order, [P] pin bones.
 hipError_t launch_fk(hipStream_t st, int count, int B, int P, int S, int levels, const int *sched, const float *pose,
 		const float *inv_bind, float *globals, const float *targets, float *pin_distance);
-// k_skin.hip: mbik_skin_vertices (skin.h).  Grid = ceil(count / S) skeleton tiles x `chunks` vertex chunks of `chunk`
-// vertices; S * B * 48 bytes of LDS a block; the block's 256 threads are (1 << vshift) vertex lanes (64, 128 or 256)
-// by 256 >> vshift skeleton groups.  mesh is the device copy in skin_layout()'s planes; out_n null = positions only.
-hipError_t launch_skin(hipStream_t st, int K, int count, int B, int V, int S, int chunk, int chunks, int vshift,
-		const unsigned char *mesh, bool mesh_normals, const float *skin, float *out_p, float *out_n);
-// k_skin.hip: mbik_skin_vertices_shaped (morph.h).  The same grid and block; S * (B * 48 + P * 4) bytes of LDS a block (the
-// tile's shape weights behind its matrices); mesh carries morph_layout()'s shape planes behind skin_layout()'s; shape_weights
-// is device memory [count][P]; mode is a MorphMode.
-hipError_t launch_skin_shaped(hipStream_t st, int K, int mode, int count, int B, int V, int P, int S, int chunk, int chunks, int vshift,
-		const unsigned char *mesh, bool mesh_normals, const float *skin, const float *shape_weights, float *out_p, float *out_n);
-// k_skin_list.hip: mbik_skin_vertices_listed (skin_list.h).  launch_skin's block (shape_weights null) or launch_skin_shaped's,
-// with the same LDS; grid = ceil(max_list / S) tiles of list entries x `chunks` vertex chunks, S <= 64 and max_list >= 1.  indices
-// (device, [max_list]) and list_count (device, [1]) are read by the kernel only, which tests every entry against [0, count);
-// compact: entry r writes output row r, otherwise row indices[r].
-hipError_t launch_skin_listed(hipStream_t st, int K, int mode, int count, int B, int V, int P, int S, int chunk, int chunks, int vshift,
-		const unsigned char *mesh, bool mesh_normals, const float *skin, const float *shape_weights, const int32_t *indices,
-		const int32_t *list_count, int max_list, bool compact, float *out_p, float *out_n);
+// A skinning launch (k_skin.hip, k_skin_list.hip; the shared body and launch are skin_dev.h's).  The grid is tiles x `chunks`
+// vertex chunks of `chunk` vertices; the block's 256 threads are (1 << vshift) vertex lanes (64, 128 or 256) by 256 >> vshift
+// groups that share a tile's S slots.  mesh is the device copy in skin_layout()'s planes, with morph_layout()'s shape planes
+// behind them when the mesh has shapes; out_n null = positions only.  shape_weights (device, [count][P]) null = no shapes:
+// S * B * 48 bytes of LDS a block, otherwise S * (B * 48 + P * 4), the tile's shape weights behind its matrices; mode is
+// the mesh's MorphMode.
+struct SkinLaunch {
+	hipStream_t st;
+	int K, mode, count, B, V, P, S, chunk, chunks, vshift;
+	const unsigned char *mesh;
+	bool mesh_normals;
+	const float *skin, *shape_weights;
+	float *out_p, *out_n;
+	// launch_skin_listed only: indices (device, [max_list]) and list_count (device, [1]) are read by the kernel only, which
+	// tests every entry against [0, count); compact: entry r writes output row r, otherwise row indices[r]
+	const int32_t *indices, *list_count;
+	int max_list;
+	bool compact;
+};
+// k_skin.hip: mbik_skin_vertices (skin.h) and, with shape_weights, mbik_skin_vertices_shaped (morph.h).  A tile is S
+// consecutive skeletons: ceil(count / S) tiles.
+hipError_t launch_skin(const SkinLaunch &a);
+// k_skin_list.hip: mbik_skin_vertices_listed (skin_list.h).  A tile is S list entries: ceil(max_list / S) tiles, S <= 64 and
+// max_list >= 1.
+hipError_t launch_skin_listed(const SkinLaunch &a);
 // k_bounds.hip: mbik_skin_bounds (bounds.h).  Grid = ceil(count / S) blocks of S skeletons, S * max(B, 1) * 48 bytes of LDS a
 // block (the matrices; the transformed boxes overwrite them); table is the device copy of the U used bones' records
 // (bone_table_pack), U may be 0.

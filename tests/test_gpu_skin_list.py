@@ -3,7 +3,8 @@ mbik_skin_vertices_cpu / mbik_skin_vertices_shaped_cpu, bitwise (two NaNs count 
 is compared whole with tests/skin_list_cases.expected, so a listed row must carry the existing call's
 bits and every other row its sentinel, and has a row and more of sentinels in front and behind.  skin
 and shape_weights sit between a skeleton's worth of NaN on either side: a wrong range guard shows as a
-failed compare.  Tile boundaries, empty tiles, the twelve instantiations, index patterns, out-of-range
+failed compare.  Tile boundaries, empty tiles, the twelve instantiations, the identity list against the
+plain and the shaped call on the device (all twelve again, bitwise), index patterns, out-of-range
 entries, vertex lanes and chunks, shaped meshes, float-aligned buffers, the LDS limits, offsets past
 2^31, the whole frame on one stream, error codes."""
 import ctypes as C
@@ -123,6 +124,44 @@ def test_tile_boundaries(mbik, torch_dev, B, K, normals):
         # counts the kernel clamps: negative, and above max_list
         check_listed(torch, dev, mesh, d, cyclic_list(5, count, big), -4, big, True, False, normals)
         check_listed(torch, dev, mesh, d, cyclic_list(6, count, Sx + 1), 2 ** 31 - 1, Sx + 1, False, False, normals)
+
+
+# ---------------- the identity list against the plain and the shaped call, device with device ----------------
+@pytest.mark.parametrize("mode", [None, "relative", "normalized"], ids=["plain", "relative", "normalized"])
+@pytest.mark.parametrize("normals", [False, True], ids=["positions", "normals"])
+@pytest.mark.parametrize("K", [4, 8])
+def test_identity_list_is_the_direct_call(mbik, torch_dev, K, normals, mode):
+    """The list 0 .. count-1, in place and compact, writes bitwise the rows mbik_skin_vertices /
+    mbik_skin_vertices_shaped write from the same buffers: the two kernel families run one vertex loop.  Two full
+    tiles and a last tile of one skeleton, more than one vertex chunk with the last one partial."""
+    torch, dev = torch_dev
+    B, V, P = 32, 700, 3 if mode else 0
+    case = LC.Case(8000 + 10 * K + P + (mode == "normalized"), B, V, K, 2 * TILE[B] + 1, P=P, mode=mode or "relative",
+                   special_weights=bool(P))
+    count = case.count
+    d = DeviceCase(torch, dev, case)
+    t_ind, p_ind, t_cnt = list_buffers(torch, dev, np.arange(count), count, count)
+
+    def outputs():
+        return Outputs(torch, dev, count, V), (Outputs(torch, dev, count, V) if normals else None)
+
+    with Mesh(B, case.pos, case.idx, case.w, **case.mesh_kw()) as mesh:
+        Sx, chunks = mesh.launch_shape(count)
+        assert Sx == TILE[B] and count == 2 * Sx + 1 and chunks > 1 and V % 256 != 0   # (a chunk is a multiple of 256 vertices)
+        direct_p, direct_n = outputs()
+        mesh.skin(d.skin_ptr, direct_p.ptr, count, out_normals_ptr=direct_n.ptr if normals else 0, shape_weights_ptr=d.w_ptr)
+        listed = []
+        for compact in (False, True):
+            out_p, out_n = outputs()
+            mesh.skin_listed(d.skin_ptr, out_p.ptr, count, p_ind, t_cnt[1:].data_ptr(), compact=compact,
+                             out_normals_ptr=out_n.ptr if normals else 0, shape_weights_ptr=d.w_ptr)
+            listed.append((out_p, out_n))
+        torch.cuda.synchronize()
+    full_p, full_n = case.full(bool(P))
+    assert S.same_bits(direct_p.read(), full_p) and (not normals or S.same_bits(direct_n.read(), full_n))
+    for out_p, out_n in listed:
+        assert torch.equal(out_p.t.view(torch.int32), direct_p.t.view(torch.int32))
+        assert not normals or torch.equal(out_n.t.view(torch.int32), direct_n.t.view(torch.int32))
 
 
 # ---------------- index patterns ----------------
