@@ -34,6 +34,12 @@ namespace mbik_host {
 // The calling thread's last error message (mbik_last_error) and the error-return helper.
 extern thread_local std::string g_err;
 int fail(int code, const std::string &msg);
+// Puts the last error message back at the end of its scope, for a caller that asks a function
+// which reports through fail() a question whose "no" is not the caller's failure.
+struct KeepError {
+	std::string saved = g_err;
+	~KeepError() { g_err = saved; }
+};
 
 struct DeviceGuard {
 	int prev = -1;
@@ -87,6 +93,18 @@ struct LayoutPins {
 	int roles = -1;                       // mbik_plan_set_wave_roles; -1 = automatic (off until autotuned)
 	int cm_lanes = 0;                     // constraint_mode: lanes per skeleton (0 = auto)
 	int cm_spw_div = 0;                   // constraint_mode: skeletons per wave = (64 / K) >> cm_spw_div
+	bool operator==(const LayoutPins &o) const {
+		return lanes == o.lanes && spw == o.spw && interval == o.interval && staging == o.staging && locals == o.locals &&
+				waves == o.waves && helper == o.helper && roles == o.roles && cm_lanes == o.cm_lanes && cm_spw_div == o.cm_spw_div;
+	}
+};
+
+// What the uploaded topology blob (mbik_plan::topo, with the lane schedule) was packed for.
+struct BlobKey {
+	int K = -1, interval = -1, staging = -1, placement = -1, roles = -1;
+	bool operator==(const BlobKey &o) const {
+		return K == o.K && interval == o.interval && staging == o.staging && placement == o.placement && roles == o.roles;
+	}
 };
 
 } // namespace mbik_host
@@ -114,9 +132,8 @@ struct mbik_plan {
 	int64_t device_bytes = 0;
 	double alg_bytes = 0;
 	double alg_flops = 0;
-	int sched_K = -1, sched_c = -1, sched_staging = -1; // layout of the uploaded topology blob
+	mbik_host::BlobKey blob_key;                         // layout of the uploaded topology blob (invalidate_layout)
 	int tab64 = 0;                                       // mbik_plan_set_table_addressing
-	int sched_locals = -1, sched_roles = -1;
 	// tables uploaded once and never resized: D / CF / CD, constraint_mode's pre-order tables, the
 	// setup view's (mbik_plan_rebuild_setup); dev, cm and dsetup point into them
 	std::vector<mbik_host::DevBuf> uploads;
@@ -197,20 +214,53 @@ int check_mesh(int32_t B, int32_t V, int32_t K, const float *positions, const in
 // placements 1 and 2, and the setup tables of every layout that can (kTab32 / kTabTiled)
 constexpr size_t kMaxBufBytes = 0xFFFFFFF0u;
 bool tables_fit_32(const mbik_plan *p);
-mbik::SolveKernel solve_kernel_for(const mbik_plan *p);
-bool helper_on(const mbik_plan *p);
 int take_helper_timeout(mbik_plan *p);
+// Resident one-wave blocks per CU at a block LDS size (ctx: the plan), for build_schedule.
 int blocks_per_cu(void *ctx, int64_t lds_bytes);
+// A setter changed a pin: the next ensure_schedule packs and uploads the topology blob again.
+inline void invalidate_layout(mbik_plan *p) { p->blob_key = BlobKey{}; }
+// pins -> LayoutRequest -> build_schedule -> (buffers, topology blob) for a launch of nlaunch skeletons.
 int ensure_schedule(mbik_plan *p, int64_t nlaunch);
-int launch(mbik_plan *p, int first, int count, const float *pose_in, const float *targets, float *pose_out, hipStream_t stream,
-		int iterations, int seg_lo, int seg_hi);
 
-// constraint_mode launch shape and node-cache layout conversions (host_plan.cpp)
-struct CmShape {
-	int spw, wpb;
+// One solve launch of the plan's current layout (ensure_schedule), resolved: the only place that
+// picks the kernel, the grid and the LDS.  launch(), mbik_plan_get_info, mbik_group_solve and the
+// autotune read it.
+struct SolveLaunch {
+	bool cmode = false;                // which handle the launch takes: cm (constraint_mode) or solve
+	mbik::SolveKernel solve = nullptr;
+	mbik::CmodeKernel cm = nullptr;
+	unsigned blocks = 0, threads = 64;
+	size_t lds_bytes = 0;              // the launch's dynamic LDS
+	// What mbik_plan_get_info reports as lds_bytes_per_block.  constraint_mode: lds_bytes.  Else
+	// build_schedule's figure for its last launch size (HostPlan::lds_block_bytes): the classic
+	// block before the blob was packed, without the helper ring.  Kept as reported so far.
+	int64_t schedule_lds_bytes = 0;
+	int skeletons_per_block = 0;
+	int cm_spw = 0, cm_wpb = 0;        // constraint_mode: skeletons per wave, waves per block (CmodeState)
+	bool wave_roles = false;           // a wave per role (either kernel family)
+	bool helper = false;               // the helper-wave kernel (128 threads, or 64 when replaying)
+	bool needs_flag = false;           // the kernel reports a handshake timeout: the plan's flag word (ensure_help_flag)
+	bool tiled_rows = false;           // the kernel reads the skeleton-tiled D / CF / CD (ensure_tiled_rows)
 };
-CmShape cmode_shape_of(const mbik_plan *p, int64_t count);
-size_t cmode_lds_bytes(const mbik_plan *p, CmShape sh);
+// MBIK_OK, or the refusal of a block that exceeds the LDS (MBIK_EUNSUPPORTED) or of an impossible
+// role count (MBIK_EINVAL).  No allocation, no HIP call.  replay: MBIK_REPLAY's DevPlan::replay.
+int resolve_launch(const mbik_plan *p, int64_t count, SolveLaunch &out, int replay = 0);
+
+// One solve of skeletons [first, first + count); nonfinite and replay reach the kernel through a
+// copy of the plan's DevPlan / CmodeState: a launch leaves the plan's own as they were.
+struct LaunchArgs {
+	int first, count;
+	const float *pose_in, *targets;
+	float *pose_out;
+	hipStream_t stream;
+	int iterations, seg_lo, seg_hi;
+	unsigned char *nonfinite = nullptr;
+	int replay = 0;
+};
+// The whole-skeleton solve of mbik_solve (every iteration, every segment).
+LaunchArgs full_solve(const mbik_plan *p, int first, int count, const float *pose_in, const float *targets, float *pose_out, hipStream_t stream);
+int launch(mbik_plan *p, const LaunchArgs &a);
+
 // constraint_mode state in device memory and in a plan file: node caches, then dirty words
 size_t cmode_node_bytes(const mbik::HostPlan &h);
 size_t cmode_dirty_bytes(const mbik::HostPlan &h);

@@ -125,8 +125,8 @@ bool tables_fit_32(const mbik_plan *p) {
 }
 // The solve kernel instantiation of a plan's current layout (stabilization x locals placement
 // x waves per SIMD, and for placement 0 the table addressing): k_solve_w1.hip, k_solve_w2.hip,
-// k_solve_rw.hip.
-mbik::SolveKernel solve_kernel_for(const mbik_plan *p) {
+// k_solve_rw.hip.  Never the helper-wave kernel: resolve_launch swaps that in.
+static mbik::SolveKernel solve_kernel_for(const mbik_plan *p) {
 	const mbik::HostPlan &h = p->host;
 	if (h.wave_roles) return mbik::solve_kernel_rw(h.K, h.waves_per_simd, p->dev.prio_mask);
 	const int pl = std::min(2, std::max(0, (int)h.state_hbm));
@@ -145,7 +145,7 @@ static size_t block_lds_bytes(const mbik_plan *p) {
 // Whether a launch of the plan's current layout runs with the helper wave
 // (mbik_solve_kernel_help): asked for, and a layout it serves -- state in LDS, no
 // stabilization, one wave per SIMD, 32-bit tables -- whose block LDS still fits with the ring.
-bool helper_on(const mbik_plan *p) {
+static bool helper_on(const mbik_plan *p) {
 	const mbik::HostPlan &h = p->host;
 	if (p->pins.helper != 1) return false;
 	// (packed levels run row by row there: both waves walk the same rows)
@@ -188,6 +188,9 @@ int take_helper_timeout(mbik_plan *p) {
 
 // Resident one-wave blocks per CU for a block's LDS size, from the runtime's occupancy
 // query on the kernel instantiation the plan launches (LDS granularity and registers).
+// Deliberately the classic or wave-roles kernel of the layout at 64 threads, also where the
+// launch runs the helper-wave kernel or K waves per block: build_schedule's choice of skeletons
+// per block and checkpoint interval depends on this answer, so changing the query changes layouts.
 int blocks_per_cu(void *ctx, int64_t lds_bytes) {
 	const mbik_plan *p = static_cast<const mbik_plan *>(ctx);
 	int n = 0;
@@ -209,70 +212,109 @@ static int64_t cmode_rw_lds(const mbik::HostPlan &h, int64_t topo_bytes, int64_t
 	return topo_bytes + (2 * (int64_t)h.B + spw * 4 * h.cm_dirty_words() + (int64_t)h.K * 64 * h.cm_maxd + (int64_t)h.K * 4 * 64 + 64) * 4;
 }
 
-// roles_ok false: the classic layout even where wave roles are asked for (their block does not
-// fit the LDS, below).
-static int ensure_schedule_as(mbik_plan *p, int64_t nlaunch, bool roles_ok) {
+// constraint_mode block LDS (cmode.h): the topology blob and pre-order tables once per block;
+// per wave the dirty words of its spw skeletons, and per lane the chain stack and, with
+// stabilization, the target-heading origins.
+static size_t cmode_wave_words(const mbik_plan *p, int spw) {
+	const mbik::HostPlan &h = p->host;
+	return (size_t)spw * 4 * p->cm.W + 64 * ((size_t)p->cm.maxd + (h.stabilization_passes > 0 ? 3 * (size_t)h.P : 0));
+}
+// constraint_mode launch shape: spw skeletons per wave (cm_spw_div halves 64 / K that many
+// times), and as many waves per block (<= kCmodeMaxWaves) as share the block's LDS within
+// kLdsBytes and leave the launch with at least one block per CU.
+struct CmShape {
+	int spw, wpb;
+};
+static CmShape cmode_shape_of(const mbik_plan *p, int64_t count) {
+	const mbik::HostPlan &h = p->host;
+	if (h.cm_roles) // wave roles: a block is K waves x spw skeletons (64, halved cm_spw_div times)
+		return CmShape{p->pins.spw > 0 ? std::min(64, p->pins.spw) : std::max(1, 64 >> std::max(0, p->pins.cm_spw_div)), 1};
+	const int full = 64 >> h.log2K;
+	const int spw = p->pins.spw > 0 ? std::min(full, p->pins.spw) : std::max(1, full >> std::max(0, p->pins.cm_spw_div));
+	int wpb = kCmodeMaxWaves;
+	const size_t fixed = (size_t)p->dev.topo_words + 2 * (size_t)h.B;
+	while (wpb > 1 && ((fixed + (size_t)wpb * cmode_wave_words(p, spw)) * sizeof(float) > (size_t)mbik::kLdsBytes ||
+							  (size_t)(count + (int64_t)wpb * spw - 1) / ((size_t)wpb * spw) < (size_t)p->cu_count))
+		wpb >>= 1;
+	return CmShape{spw, wpb};
+}
+static size_t cmode_lds_bytes(const mbik_plan *p, CmShape sh) {
+	const mbik::HostPlan &h = p->host;
+	if (h.cm_roles) return (size_t)cmode_rw_lds(h, (int64_t)p->dev.topo_words * 4, sh.spw);
+	return ((size_t)p->dev.topo_words + 2 * (size_t)h.B + (size_t)sh.wpb * cmode_wave_words(p, sh.spw)) * sizeof(float);
+}
+
+// The pins resolved to what build_schedule is asked for: decisions only, no device allocation and
+// no HIP call.  It does write p->host: the role-count probe is a whole build_schedule (without the
+// occupancy query) of which only K is read, and the build that follows in ensure_schedule_as
+// overwrites the rest.  A refusal returns before that build, so the plan keeps the launch shape
+// of its last successful ensure_schedule (or the probe's), not the refused one.
+// roles_ok false: the classic layout even where wave roles are asked for (ensure_schedule_as).
+static int request_for(mbik_plan *p, int64_t nlaunch, bool roles_ok, mbik::LayoutRequest &rq) {
 	mbik::HostPlan &h = p->host;
-	int lanes = p->pins.lanes;
-	if (lanes == 0 && h.constraint_mode && p->pins.cm_lanes > 0) lanes = p->pins.cm_lanes;
-	h.staging = p->pins.staging < 0 ? 1 : p->pins.staging;
-	h.state_hbm = h.constraint_mode ? 0 : std::max(0, p->pins.locals);
-	h.waves_per_simd = (p->pins.waves == 2 && !h.constraint_mode && h.stabilization_passes == 0) ? 2 : 1;
+	rq = mbik::LayoutRequest{};
+	rq.lanes = p->pins.lanes;
+	rq.spw = p->pins.spw;
+	rq.interval = p->pins.interval;
+	if (rq.lanes == 0 && h.constraint_mode && p->pins.cm_lanes > 0) rq.lanes = p->pins.cm_lanes;
+	rq.staging = p->pins.staging < 0 ? 1 : p->pins.staging;
+	rq.state_hbm = h.constraint_mode ? 0 : std::max(0, p->pins.locals);
+	rq.waves_per_simd = (p->pins.waves == 2 && !h.constraint_mode && h.stabilization_passes == 0) ? 2 : 1;
 	// Wave roles (mbik_plan_set_wave_roles): the whole state in device memory, one wave per role
 	// (K = 2, 4 or 8 waves per block; 8 only at two waves per SIMD), no stabilization, 32-bit tables.
-	h.wave_roles = roles_ok && p->pins.roles == 1 && !h.constraint_mode && h.stabilization_passes == 0 && tables_fit_32(p) ? 1 : 0;
-	if (h.wave_roles) {
-		const int cap = 4 * h.waves_per_simd;
-		int roles = std::min(lanes, cap);
+	if (roles_ok && p->pins.roles == 1 && !h.constraint_mode && h.stabilization_passes == 0 && tables_fit_32(p)) {
+		const int cap = 4 * rq.waves_per_simd;
+		int roles = std::min(rq.lanes, cap);
 		if (roles == 0) {
-			mbik::build_schedule(h, 0, nlaunch, 0, p->pins.interval, nullptr, nullptr, p->cu_count);
+			mbik::LayoutRequest widest;
+			widest.interval = p->pins.interval;
+			mbik::build_schedule(h, widest, nlaunch, nullptr, nullptr, p->cu_count);
 			roles = std::min(h.K, cap);
 		}
 		// one role is the classic layout with 64 skeletons per wave: no wave roles then
 		if (roles >= 2) {
-			lanes = roles;
-			h.state_hbm = 2;
-			h.staging = 0;
-		} else {
-			h.wave_roles = 0;
+			rq.lanes = roles;
+			rq.state_hbm = 2;
+			rq.staging = 0;
+			rq.wave_roles = 1;
 		}
 	}
 	// constraint_mode with wave roles (cmode.h mbik_cmode_kernel_rw): K = 2, 4 or 8 waves per block
-	h.cm_roles = 0;
 	if (roles_ok && h.constraint_mode && p->pins.roles == 1 && h.stabilization_passes == 0 && tables_fit_32(p) &&
 			cmode_node_bytes(h) < (size_t(1) << 32)) {
 		int roles = 1;
-		while (roles < (lanes > 0 ? lanes : kCmodeLanes)) roles <<= 1;
+		while (roles < (rq.lanes > 0 ? rq.lanes : kCmodeLanes)) roles <<= 1;
 		roles = std::min(8, roles);
 		if (roles >= 2) {
-			lanes = roles;
-			h.cm_roles = 1;
+			rq.lanes = roles;
+			rq.cm_roles = 1;
 		}
 	}
-	if (h.state_hbm >= 1 && !tables_fit_32(p))
+	if (rq.state_hbm >= 1 && !tables_fit_32(p))
 		return fail(MBIK_EUNSUPPORTED, "state placements 1 and 2 need every setup table < 4 GiB (fewer skeletons per plan)");
-	if (h.state_hbm >= 1 && !p->locals) {
+	// split-exchange (staging 4 / 5) runs in the 32-bit-table two-wave builds; the 64-bit-index
+	// two-wave build solves those segments alone (4 -> 0) or staged (5 -> 2)
+	if (rq.waves_per_simd == 2 && !tables_fit_32(p) && rq.staging >= 4) rq.staging = rq.staging == 4 ? 0 : 2;
+	return MBIK_OK;
+}
+
+// The placement buffers grow with the layouts a plan has run.  Placements 1 and 2: the bone locals
+// (reserved before the schedule is built, as ever: a wave-roles request that falls back to the
+// classic layout has them counted in device_bytes all the same).
+static int reserve_locals(mbik_plan *p, int state_hbm) {
+	const mbik::HostPlan &h = p->host;
+	if (state_hbm >= 1 && !p->locals) {
 		// LocTiled: whole tiles of kLocTile skeletons
 		const size_t bytes = (size_t)((h.N + kLocTile - 1) / kLocTile) * kLocTile * h.B * 12 * sizeof(float);
 		if (int rc = reserve_counted(p, p->locals, bytes, "hipMalloc locals")) return rc;
 		p->dev.Lg = p->locals.as<float>();
 		p->dev.lg_bytes = (uint32_t)std::min<size_t>(bytes, 0xFFFFFFFFu); // (placement 2 refuses > kMaxBufBytes)
 	}
-	// split-exchange (staging 4 / 5) runs in the 32-bit-table two-wave builds; the 64-bit-index
-	// two-wave build solves those segments alone (4 -> 0) or staged (5 -> 2)
-	if (h.waves_per_simd == 2 && !tables_fit_32(p) && h.staging >= 4) h.staging = h.staging == 4 ? 0 : 2;
-	mbik::build_schedule(h, lanes, nlaunch, p->pins.spw, p->pins.interval, blocks_per_cu, p, p->cu_count);
-	if (lanes == 0 && h.constraint_mode && h.K > kCmodeLanes && !h.cm_roles)
-		mbik::build_schedule(h, kCmodeLanes, nlaunch, p->pins.spw, p->pins.interval, blocks_per_cu, p, p->cu_count);
-	// A wave-roles block holds the topology, the non-finite flags and, with cooperative rows, the
-	// block's targets and the effector-global exchange (the root segment's row alone takes a slot
-	// per pin); constraint_mode's holds per-wave chain stacks of the deepest pose chain.  Where that
-	// exceeds the LDS the plan falls back to the classic layout, as it does for stabilization or
-	// 64-bit tables: a pinned mbik_plan_set_wave_roles(1) still solves, and the autotune times the
-	// classic layout for such a candidate instead of failing on it.
-	if (roles_ok && ((h.wave_roles && h.lds_block_bytes > mbik::kLdsBytes) ||
-							(h.cm_roles && cmode_rw_lds(h, mbik::topology_bytes(h), cmode_shape_of(p, nlaunch).spw) > mbik::kLdsBytes)))
-		return ensure_schedule_as(p, nlaunch, false);
+	return MBIK_OK;
+}
+// Placement 2, once the schedule says how many checkpoints a skeleton keeps.
+static int reserve_state(mbik_plan *p) {
+	const mbik::HostPlan &h = p->host;
 	if (h.state_hbm == 2) {
 		// the whole state in device memory: one skeleton's LDS layout per skeleton (the locals
 		// and the checkpoint globals live in skeleton-tiled areas, d_locals and d_gtile)
@@ -289,18 +331,19 @@ static int ensure_schedule_as(mbik_plan *p, int64_t nlaunch, bool roles_ok) {
 		p->dev.sg_bytes = (uint32_t)p->state.bytes();
 		p->dev.state_stride = stride;
 	}
-	if (p->sched_K == h.K && p->sched_c == h.g_interval && p->sched_staging == h.staging &&
-			p->sched_locals == h.state_hbm && p->sched_roles == (h.wave_roles | h.cm_roles << 1) && p->topo) {
+	return MBIK_OK;
+}
+
+// Packs and uploads the topology blob unless the one on the device was packed for this layout.
+static int upload_blob(mbik_plan *p) {
+	const mbik::HostPlan &h = p->host;
+	const BlobKey key{h.K, h.g_interval, h.staging, h.state_hbm, h.wave_roles | h.cm_roles << 1};
+	if (p->blob_key == key && p->topo) {
 		p->dev.spw = h.spw;
 		return MBIK_OK;
 	}
-	int rc = upload_topology(p);
-	if (rc) return rc;
-	p->sched_K = h.K;
-	p->sched_c = h.g_interval;
-	p->sched_staging = h.staging;
-	p->sched_locals = h.state_hbm;
-	p->sched_roles = h.wave_roles | h.cm_roles << 1;
+	if (int rc = upload_topology(p)) return rc;
+	p->blob_key = key;
 	p->dev.nrows = h.nrows;
 	p->dev.K = h.K;
 	p->dev.log2K = h.log2K;
@@ -312,43 +355,30 @@ static int ensure_schedule_as(mbik_plan *p, int64_t nlaunch, bool roles_ok) {
 	return MBIK_OK;
 }
 
-int ensure_schedule(mbik_plan *p, int64_t nlaunch) { return ensure_schedule_as(p, nlaunch, true); }
+static int ensure_schedule_as(mbik_plan *p, int64_t nlaunch, bool roles_ok) {
+	mbik::HostPlan &h = p->host;
+	mbik::LayoutRequest rq;
+	if (int rc = request_for(p, nlaunch, roles_ok, rq)) return rc;
+	if (int rc = reserve_locals(p, rq.state_hbm)) return rc;
+	mbik::build_schedule(h, rq, nlaunch, blocks_per_cu, p, p->cu_count);
+	if (rq.lanes == 0 && h.constraint_mode && h.K > kCmodeLanes && !h.cm_roles) {
+		rq.lanes = kCmodeLanes;
+		mbik::build_schedule(h, rq, nlaunch, blocks_per_cu, p, p->cu_count);
+	}
+	// A wave-roles block holds the topology, the non-finite flags and, with cooperative rows, the
+	// block's targets and the effector-global exchange (the root segment's row alone takes a slot
+	// per pin); constraint_mode's holds per-wave chain stacks of the deepest pose chain.  Where that
+	// exceeds the LDS the plan falls back to the classic layout, as it does for stabilization or
+	// 64-bit tables: a pinned mbik_plan_set_wave_roles(1) still solves, and the autotune times the
+	// classic layout for such a candidate instead of failing on it.
+	if (roles_ok && ((h.wave_roles && h.lds_block_bytes > mbik::kLdsBytes) ||
+							(h.cm_roles && cmode_rw_lds(h, mbik::topology_bytes(h), cmode_shape_of(p, nlaunch).spw) > mbik::kLdsBytes)))
+		return ensure_schedule_as(p, nlaunch, false);
+	if (int rc = reserve_state(p)) return rc;
+	return upload_blob(p);
+}
 
-// constraint_mode block LDS (cmode.h): topology blob, pre-order tables, the dirty words of
-// the block's 64 / K skeletons, then per lane the chain stack and, with stabilization, the
-// target-heading origins.
-// Per wave: the dirty words of its spw skeletons, and per lane the chain stack and (STAB) the
-// target-heading origins; the topology and pre-order tables once per block.
-static size_t cmode_wave_words(const mbik_plan *p, int spw) {
-	const mbik::HostPlan &h = p->host;
-	return (size_t)spw * 4 * p->cm.W + 64 * ((size_t)p->cm.maxd + (h.stabilization_passes > 0 ? 3 * (size_t)h.P : 0));
-}
-// constraint_mode launch shape: spw skeletons per wave (cm_spw_div halves 64 / K that many
-// times), and as many waves per block (<= kCmodeMaxWaves) as share the block's LDS within
-// kLdsBytes and leave the launch with at least one block per CU.
-CmShape cmode_shape_of(const mbik_plan *p, int64_t count) {
-	const mbik::HostPlan &h = p->host;
-	if (h.cm_roles) // wave roles: a block is K waves x spw skeletons (64, halved cm_spw_div times)
-		return CmShape{p->pins.spw > 0 ? std::min(64, p->pins.spw) : std::max(1, 64 >> std::max(0, p->pins.cm_spw_div)), 1};
-	const int full = 64 >> h.log2K;
-	const int spw = p->pins.spw > 0 ? std::min(full, p->pins.spw) : std::max(1, full >> std::max(0, p->pins.cm_spw_div));
-	int wpb = kCmodeMaxWaves;
-	const size_t fixed = (size_t)p->dev.topo_words + 2 * (size_t)h.B;
-	while (wpb > 1 && ((fixed + (size_t)wpb * cmode_wave_words(p, spw)) * sizeof(float) > (size_t)mbik::kLdsBytes ||
-							  (size_t)(count + (int64_t)wpb * spw - 1) / ((size_t)wpb * spw) < (size_t)p->cu_count))
-		wpb >>= 1;
-	return CmShape{spw, wpb};
-}
-size_t cmode_lds_bytes(const mbik_plan *p, CmShape sh) {
-	const mbik::HostPlan &h = p->host;
-	if (h.cm_roles) return (size_t)cmode_rw_lds(h, (int64_t)p->dev.topo_words * 4, sh.spw);
-	return ((size_t)p->dev.topo_words + 2 * (size_t)h.B + (size_t)sh.wpb * cmode_wave_words(p, sh.spw)) * sizeof(float);
-}
-void cmode_shape(mbik_plan *p, int count) {
-	const CmShape sh = cmode_shape_of(p, count);
-	p->cm.spw = sh.spw;
-	p->cm.wpb = sh.wpb;
-}
+int ensure_schedule(mbik_plan *p, int64_t nlaunch) { return ensure_schedule_as(p, nlaunch, true); }
 
 // Resets the constraint_mode node caches of skeletons [first, first+count) to a fresh tree
 // built on `setup_pose` (device pointer, indexed from `first`).
@@ -475,81 +505,115 @@ int wait_tiled_rows(mbik_plan *p, hipStream_t stream) {
 	return MBIK_OK;
 }
 
-int launch(mbik_plan *p, int first, int count, const float *pose_in, const float *targets, float *pose_out,
-		hipStream_t stream, int iterations, int seg_lo, int seg_hi) {
-	if (first < 0 || count < 0 || (int64_t)first + count > p->host.N) return fail(MBIK_EINVAL, "skeleton range out of plan");
-	if (count == 0) return MBIK_OK;
-	if (!pose_in || !pose_out || (p->host.P > 0 && !targets)) return fail(MBIK_EINVAL, "null buffer");
+int resolve_launch(const mbik_plan *p, int64_t count, SolveLaunch &o, int replay) {
+	const mbik::HostPlan &h = p->host;
+	o = SolveLaunch{};
+	o.wave_roles = h.wave_roles || h.cm_roles;
+	if (h.constraint_mode) {
+		const CmShape sh = cmode_shape_of(p, count);
+		o.cmode = true;
+		o.cm_spw = sh.spw;
+		o.cm_wpb = sh.wpb;
+		// (reported so: a classic constraint_mode block holds wpb waves of at most this many)
+		o.skeletons_per_block = h.cm_roles ? sh.spw : 64 >> h.log2K;
+		o.lds_bytes = cmode_lds_bytes(p, sh);
+		o.schedule_lds_bytes = (int64_t)o.lds_bytes;
+		if (o.lds_bytes > (size_t)mbik::kLdsBytes) return fail(MBIK_EUNSUPPORTED, "skeleton too large for the constraint_mode LDS layout");
+		// node caches below 4 GiB: buffer-resource addressing (cmode.h, NB32)
+		const bool nb32 = cmode_node_bytes(h) < (size_t(1) << 32) && tables_fit_32(p);
+		o.cm = mbik::cmode_kernel(h.stabilization_passes > 0, nb32, h.has_chain);
+		o.threads = 64u * (unsigned)sh.wpb;
+		if (h.cm_roles) {
+			// wave roles: K waves x spw skeletons per block (request_for: K in {2, 4, 8}, 32-bit addressing)
+			if (h.K != 2 && h.K != 4 && h.K != 8) return fail(MBIK_EINVAL, "constraint_mode wave roles: 2, 4 or 8 roles");
+			o.cm = mbik::cmode_kernel_rw(h.has_chain, h.K);
+			o.threads = 64u * (unsigned)h.K;
+		}
+		const int64_t per_block = (int64_t)sh.spw * sh.wpb;
+		o.blocks = (unsigned)((count + per_block - 1) / per_block);
+		return MBIK_OK;
+	}
+	o.skeletons_per_block = h.spw;
+	o.schedule_lds_bytes = h.lds_block_bytes;
+	o.tiled_rows = h.state_hbm == 2;
+	o.lds_bytes = block_lds_bytes(p);
+	if constexpr (kAblate & ABL_SOALDS) o.lds_bytes += ((size_t)p->dev.B * 9 + p->dev.NC * p->dev.cf_stride + 2 * p->dev.NC * p->dev.cd_stride + 2) * sizeof(float);
+	if (o.lds_bytes > (size_t)mbik::kLdsBytes) return fail(MBIK_EUNSUPPORTED, "skeleton too large for LDS at this lane count");
+	o.blocks = (unsigned)((count + h.spw - 1) / h.spw);
+	o.solve = solve_kernel_for(p);
+	if (h.wave_roles) {
+		o.threads = 64u * (unsigned)h.K; // a wave per role
+		// non-finite flags; with cooperative rows the targets, the effector-global exchange and the
+		// groups' parent-side records
+		o.lds_bytes += (size_t)mbik::rw_extra_lds_bytes(h);
+		if (o.lds_bytes > (size_t)mbik::kLdsBytes) return fail(MBIK_EUNSUPPORTED, "wave roles: a row's effector-global exchange exceeds the LDS");
+		// the cooperative groups' record handshake has a deadline and reports through the plan's
+		// timeout flag, as the helper wave's does (rw_wait)
+		o.needs_flag = h.rw_xslots != 0;
+	} else if (helper_on(p)) {
+		o.helper = o.needs_flag = true;
+		o.lds_bytes += kHelpRingBytes;
+		o.threads = replay == 2 ? 64 : 128; // (replay mode 2: the solving wave alone)
+		o.solve = mbik::solve_kernel_help(p->dev.prio_mask, replay == 2);
+	}
+	return MBIK_OK;
+}
+
+// Whether mbik_group_solve's fused kernel (one wave per block, state in LDS, 32-bit tables) serves
+// the plan's current layout.  constraint_mode plans have their own kernel, so do plans laid out
+// with state in device memory (wave roles among them), plans whose setup tables need 64-bit
+// indices and plans with split-exchange segments (the two-wave build); pinless plans only copy.
+static bool group_fusable(const mbik_plan *p) {
+	const mbik::HostPlan &h = p->host;
+	return !h.constraint_mode && h.P > 0 && h.state_hbm == 0 && tables_fit_32(p) && !h.has_xs;
+}
+
+LaunchArgs full_solve(const mbik_plan *p, int first, int count, const float *pose_in, const float *targets, float *pose_out, hipStream_t stream) {
+	return LaunchArgs{first, count, pose_in, targets, pose_out, stream, p->host.iterations, 0, p->host.NS - 1};
+}
+
+int launch(mbik_plan *p, const LaunchArgs &a) {
+	if (a.first < 0 || a.count < 0 || (int64_t)a.first + a.count > p->host.N) return fail(MBIK_EINVAL, "skeleton range out of plan");
+	if (a.count == 0) return MBIK_OK;
+	if (!a.pose_in || !a.pose_out || (p->host.P > 0 && !a.targets)) return fail(MBIK_EINVAL, "null buffer");
 	const mbik::HostPlan &h = p->host;
 	if (h.P == 0) {
 		// get_effector_count() == 0: _process_modification returns before solving
 		// (many_bone_ik_3d.cpp:649-651) and the skeleton keeps its pose.
-		if (pose_out != pose_in &&
-				hipMemcpyAsync(pose_out, pose_in, (size_t)count * h.B * 10 * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess)
+		if (a.pose_out != a.pose_in &&
+				hipMemcpyAsync(a.pose_out, a.pose_in, (size_t)a.count * h.B * 10 * sizeof(float), hipMemcpyDeviceToDevice, a.stream) != hipSuccess)
 			return fail(MBIK_EHIP, "hipMemcpyAsync");
 		return MBIK_OK;
 	}
-	int rc = ensure_schedule(p, count);
+	int rc = ensure_schedule(p, a.count);
 	if (rc) return rc;
-	if (h.constraint_mode) {
-		cmode_shape(p, count);
-		const size_t clds = cmode_lds_bytes(p, CmShape{p->cm.spw, p->cm.wpb});
-		if (clds > (size_t)mbik::kLdsBytes) return fail(MBIK_EUNSUPPORTED, "skeleton too large for the constraint_mode LDS layout");
-		// node caches below 4 GiB: buffer-resource addressing (cmode.h, NB32)
-		const bool nb32 = cmode_node_bytes(h) < (size_t(1) << 32) && tables_fit_32(p);
-		mbik::CmodeKernel ck = mbik::cmode_kernel(h.stabilization_passes > 0, nb32, h.has_chain);
-		const int per_block = p->cm.spw * p->cm.wpb;
-		unsigned threads = 64 * p->cm.wpb;
-		if (h.cm_roles) {
-			// wave roles: K waves x spw skeletons per block (ensure_schedule: K in {2, 4, 8}, 32-bit addressing)
-			if (h.K != 2 && h.K != 4 && h.K != 8) return fail(MBIK_EINVAL, "constraint_mode wave roles: 2, 4 or 8 roles");
-			ck = mbik::cmode_kernel_rw(h.has_chain, h.K);
-			threads = 64 * h.K;
-		}
-		hipLaunchKernelGGL(ck, dim3((unsigned)((count + per_block - 1) / per_block)), dim3(threads), clds, stream, p->dev,
-				p->cm, first, count, pose_in, targets, pose_out, iterations, seg_lo, seg_hi);
-		hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return fail(MBIK_EHIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
-		return MBIK_OK;
-	}
-	size_t lds = block_lds_bytes(p);
-	if constexpr (kAblate & ABL_SOALDS) lds += ((size_t)p->dev.B * 9 + p->dev.NC * p->dev.cf_stride + 2 * p->dev.NC * p->dev.cd_stride + 2) * sizeof(float);
-	if (lds > (size_t)mbik::kLdsBytes) return fail(MBIK_EUNSUPPORTED, "skeleton too large for LDS at this lane count");
-	unsigned blocks = (unsigned)((count + h.spw - 1) / h.spw);
-	auto kern = solve_kernel_for(p);
-	unsigned threads = 64;
-	if (h.wave_roles) {
-		threads = 64u * (unsigned)h.K; // a wave per role
-		// non-finite flags; with cooperative rows the targets, the effector-global exchange and the
-		// groups' parent-side records
-		lds += (size_t)mbik::rw_extra_lds_bytes(h);
-		if (lds > (size_t)mbik::kLdsBytes) return fail(MBIK_EUNSUPPORTED, "wave roles: a row's effector-global exchange exceeds the LDS");
-		// the cooperative groups' record handshake has a deadline and reports through the plan's
-		// timeout flag, as the helper wave's does (rw_wait)
-		if (h.rw_xslots && (rc = ensure_help_flag(p)) != MBIK_OK) return rc;
-	} else if (helper_on(p)) {
-		if ((rc = ensure_help_flag(p)) != MBIK_OK) return rc;
-		lds += kHelpRingBytes;
-		threads = 128;
-#ifdef MBIK_REPLAY
-		const bool replay = p->dev.replay == 2;
-		if (replay) threads = 64;
-#else
-		const bool replay = false;
-#endif
-		kern = mbik::solve_kernel_help(p->dev.prio_mask, replay);
-	}
+	SolveLaunch sl;
+	if ((rc = resolve_launch(p, a.count, sl, a.replay)) != MBIK_OK) return rc;
+	if (sl.needs_flag && (rc = ensure_help_flag(p)) != MBIK_OK) return rc;
+	// the kernels take copies: what belongs to this call alone never reaches the plan's own
 	DevPlan d = p->dev;
-	if (h.state_hbm == 2) {
-		if ((rc = ensure_tiled_rows(p, stream)) != MBIK_OK) return rc;
-		if ((rc = wait_tiled_rows(p, stream)) != MBIK_OK) return rc;
+	d.nonfinite = a.nonfinite;
+#ifdef MBIK_REPLAY
+	d.replay = a.replay;
+#endif
+	if (sl.tiled_rows) {
+		if ((rc = ensure_tiled_rows(p, a.stream)) != MBIK_OK) return rc;
+		if ((rc = wait_tiled_rows(p, a.stream)) != MBIK_OK) return rc;
 		d.D = p->Dt.as<float>();
 		d.CF = p->CFt.as<float>();
 		d.CD = p->CDt.as<double>();
 		d.row_n = (int)h.padded_n();
 	}
-	hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, stream, d, first, count, pose_in, targets, pose_out,
-			iterations, seg_lo, seg_hi);
+	if (sl.cmode) {
+		CmodeState c = p->cm;
+		c.spw = sl.cm_spw;
+		c.wpb = sl.cm_wpb;
+		hipLaunchKernelGGL(sl.cm, dim3(sl.blocks), dim3(sl.threads), sl.lds_bytes, a.stream, d, c, a.first, a.count, a.pose_in, a.targets,
+				a.pose_out, a.iterations, a.seg_lo, a.seg_hi);
+	} else {
+		hipLaunchKernelGGL(sl.solve, dim3(sl.blocks), dim3(sl.threads), sl.lds_bytes, a.stream, d, a.first, a.count, a.pose_in, a.targets,
+				a.pose_out, a.iterations, a.seg_lo, a.seg_hi);
+	}
 	hipError_t e = hipGetLastError();
 	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
 	return MBIK_OK;
@@ -724,6 +788,11 @@ int32_t mbik_plan_get_info(const mbik_plan *p, mbik_plan_info *o) {
 	const mbik::HostPlan &h = p->host;
 	int maxh = 0;
 	for (int i = 0; i < h.NS; i++) maxh = std::max(maxh, h.seg_height[i]);
+	// the launch of the whole plan, independent of earlier launches' counts (a block that exceeds
+	// the LDS is still reported: the refusal belongs to the solve)
+	SolveLaunch sl;
+	const KeepError keep; // (a report is no failure: mbik_last_error stays as it was)
+	(void)resolve_launch(p, h.N, sl);
 	o->abi_version = MBIK_ABI_VERSION;
 	o->skeleton_count = h.N;
 	o->bone_count = h.B;
@@ -731,14 +800,13 @@ int32_t mbik_plan_get_info(const mbik_plan *p, mbik_plan_info *o) {
 	o->segment_count = h.NS;
 	o->level_count = maxh + 1;
 	o->lanes_per_skeleton = h.K;
-	o->skeletons_per_block = h.constraint_mode ? (h.cm_roles ? cmode_shape_of(p, h.N).spw : 64 >> h.log2K) : h.spw;
+	o->skeletons_per_block = sl.skeletons_per_block;
 	o->max_headings = h.max_headings;
 	o->device = p->device;
 	o->device_bytes = p->device_bytes;
 	o->algorithmic_bytes_per_skeleton = p->alg_bytes;
 	o->algorithmic_flops_per_skeleton = p->alg_flops;
-	// (constraint_mode: the block of a whole-plan launch, independent of earlier launches' counts)
-	o->lds_bytes_per_block = h.constraint_mode ? (int64_t)cmode_lds_bytes(p, cmode_shape_of(p, h.N)) : p->host.lds_block_bytes;
+	o->lds_bytes_per_block = sl.schedule_lds_bytes; // (not the launch's: SolveLaunch)
 	o->checkpoint_interval = h.g_interval;
 	o->heading_staging = h.staging;
 	o->state_placement = h.state_hbm;
@@ -747,9 +815,9 @@ int32_t mbik_plan_get_info(const mbik_plan *p, mbik_plan_info *o) {
 	o->cf_stride = h.cf_stride();
 	o->cd_stride = h.cd_stride();
 	o->libm_variant = h.libm_variant;
-	o->helper_wave = helper_on(p) ? 1 : 0;
+	o->helper_wave = sl.helper ? 1 : 0;
 	o->heading_slots = p->dev.prio_mask;
-	o->wave_roles = h.wave_roles | h.cm_roles;
+	o->wave_roles = sl.wave_roles ? 1 : 0;
 	return MBIK_OK;
 }
 
@@ -757,7 +825,7 @@ int32_t mbik_plan_set_launch(mbik_plan *p, int32_t lanes) {
 	if (!p) return fail(MBIK_EINVAL, "null plan");
 	if (lanes < 0 || lanes > 64 || (lanes & (lanes - 1))) return fail(MBIK_EINVAL, "lanes_per_skeleton must be 0 or a power of two <= 64");
 	p->pins.lanes = lanes;
-	p->sched_K = -1;
+	invalidate_layout(p);
 	return MBIK_OK;
 }
 
@@ -769,7 +837,7 @@ int32_t mbik_plan_set_layout(mbik_plan *p, int32_t lanes, int32_t skeletons_per_
 	p->pins.lanes = lanes;
 	p->pins.spw = skeletons_per_block;
 	p->pins.interval = global_checkpoint_interval;
-	p->sched_K = -1;
+	invalidate_layout(p);
 	return MBIK_OK;
 }
 
@@ -777,13 +845,15 @@ int32_t mbik_plan_set_waves_per_simd(mbik_plan *p, int32_t waves) {
 	if (!p) return fail(MBIK_EINVAL, "null plan");
 	if (waves != -1 && waves != 1 && waves != 2) return fail(MBIK_EINVAL, "waves_per_simd must be -1 (automatic), 1 or 2");
 	p->pins.waves = waves;
-	p->sched_K = -1;
+	invalidate_layout(p);
 	return MBIK_OK;
 }
 
 int32_t mbik_plan_set_helper_wave(mbik_plan *p, int32_t helper) {
 	if (!p) return fail(MBIK_EINVAL, "null plan");
 	if (helper < -1 || helper > 1) return fail(MBIK_EINVAL, "helper wave must be -1 (automatic), 0 (off) or 1 (on)");
+	// no invalidate_layout: the helper wave changes neither the schedule nor the topology blob,
+	// only the kernel and the LDS resolve_launch picks
 	p->pins.helper = helper;
 	return MBIK_OK;
 }
@@ -792,7 +862,7 @@ int32_t mbik_plan_set_wave_roles(mbik_plan *p, int32_t roles) {
 	if (!p) return fail(MBIK_EINVAL, "null plan");
 	if (roles < -1 || roles > 1) return fail(MBIK_EINVAL, "wave roles must be -1 (automatic), 0 (off) or 1 (on)");
 	p->pins.roles = roles;
-	p->sched_K = -1;
+	invalidate_layout(p);
 	return MBIK_OK;
 }
 
@@ -800,7 +870,7 @@ int32_t mbik_plan_set_table_addressing(mbik_plan *p, int32_t wide) {
 	if (!p) return fail(MBIK_EINVAL, "null plan");
 	if (wide != 0 && wide != 1) return fail(MBIK_EINVAL, "table addressing must be 0 (automatic) or 1 (64-bit indices)");
 	p->tab64 = wide;
-	p->sched_K = -1;
+	invalidate_layout(p);
 	return MBIK_OK;
 }
 
@@ -809,7 +879,7 @@ int32_t mbik_plan_set_locals_placement(mbik_plan *p, int32_t placement) {
 	if (placement < -1 || placement > 2)
 		return fail(MBIK_EINVAL, "placement must be -1 (automatic), 0 (LDS), 1 (locals in device memory) or 2 (all state)");
 	p->pins.locals = placement;
-	p->sched_K = -1;
+	invalidate_layout(p);
 	return MBIK_OK;
 }
 
@@ -817,7 +887,7 @@ int32_t mbik_plan_set_heading_staging(mbik_plan *p, int32_t staging) {
 	if (!p) return fail(MBIK_EINVAL, "null plan");
 	if (staging < -1 || staging > 5) return fail(MBIK_EINVAL, "staging must be -1 (automatic), 0, 1, 2, 3, 4 or 5");
 	p->pins.staging = staging;
-	p->sched_K = -1;
+	invalidate_layout(p);
 	return MBIK_OK;
 }
 
@@ -896,7 +966,7 @@ int32_t mbik_solve(mbik_plan *p, int32_t first, int32_t count, const float *pose
 	if (!p) return fail(MBIK_EINVAL, "null plan");
 	if (int rc = take_helper_timeout(p)) return rc;
 	DeviceGuard guard(p->device);
-	return launch(p, first, count, pose_in, targets, pose_out, (hipStream_t)stream, p->host.iterations, 0, p->host.NS - 1);
+	return launch(p, full_solve(p, first, count, pose_in, targets, pose_out, (hipStream_t)stream));
 }
 
 int32_t mbik_plan_status(const mbik_plan *p, uint32_t *status) {
@@ -922,10 +992,9 @@ int32_t mbik_solve_checked(mbik_plan *p, int32_t first, int32_t count, const flo
 	if (p->host.P == 0 && count > 0 && first >= 0 && (int64_t)first + count <= p->host.N &&
 			hipMemsetAsync(nonfinite, 0, (size_t)count, (hipStream_t)stream) != hipSuccess)
 		return fail(MBIK_EHIP, "hipMemsetAsync");
-	p->dev.nonfinite = nonfinite;
-	const int rc = launch(p, first, count, pose_in, targets, pose_out, (hipStream_t)stream, p->host.iterations, 0, p->host.NS - 1);
-	p->dev.nonfinite = nullptr;
-	return rc;
+	LaunchArgs a = full_solve(p, first, count, pose_in, targets, pose_out, (hipStream_t)stream);
+	a.nonfinite = nonfinite;
+	return launch(p, a);
 }
 
 int32_t mbik_segment_solve(mbik_plan *p, int32_t seg, int32_t first, int32_t count, float *pose_inout, const float *targets,
@@ -934,7 +1003,7 @@ int32_t mbik_segment_solve(mbik_plan *p, int32_t seg, int32_t first, int32_t cou
 	if (seg < 0 || seg >= p->host.NS) return fail(MBIK_EINVAL, "segment out of range");
 	if (int rc = take_helper_timeout(p)) return rc;
 	DeviceGuard guard(p->device);
-	return launch(p, first, count, pose_inout, targets, pose_inout, (hipStream_t)stream, 1, p->host.seg_tin[seg], seg);
+	return launch(p, LaunchArgs{first, count, pose_inout, targets, pose_inout, (hipStream_t)stream, 1, p->host.seg_tin[seg], seg});
 }
 
 int32_t mbik_group_create(mbik_plan *const *plans, int32_t n_plans, mbik_group **out_group) {
@@ -990,22 +1059,20 @@ int32_t mbik_group_solve(mbik_group *g, const int32_t *first, const int32_t *cou
 		if (!pose_in[i] || !pose_out[i] || (p->host.P > 0 && !targets[i])) return fail(MBIK_EINVAL, "null buffer");
 		int rc = p->host.P > 0 ? ensure_schedule(p, c) : MBIK_OK;
 		if (rc) return rc;
-		if (p->host.constraint_mode || p->host.P == 0 || p->host.state_hbm != 0 || !tables_fit_32(p) || p->host.has_xs) {
-			// constraint_mode plans have their own kernel, so do plans laid out with their
-			// locals in HBM, plans whose setup tables need 64-bit indices and plans with
-			// split-exchange segments (the two-wave build); pinless plans only copy
-			rc = launch(p, f, c, pose_in[i], targets[i], pose_out[i], stream, p->host.iterations, 0, p->host.NS - 1);
+		if (!group_fusable(p)) {
+			rc = launch(p, full_solve(p, f, c, pose_in[i], targets[i], pose_out[i], stream));
 			if (rc) return rc;
 			continue;
 		}
 		const mbik::HostPlan &h = p->host;
-		const size_t l = block_lds_bytes(p);
-		if (l > (size_t)mbik::kLdsBytes) return fail(MBIK_EUNSUPPORTED, "skeleton too large for LDS at this lane count");
-		lds = std::max(lds, l);
+		SolveLaunch sl;
+		if ((rc = resolve_launch(p, c, sl)) != MBIK_OK) return rc;
+		// (the fused kernel runs the classic block also for a plan with the helper wave on)
+		lds = std::max(lds, sl.lds_bytes - (sl.helper ? kHelpRingBytes : 0));
 		stab = stab || h.stabilization_passes > 0;
 		dp.push_back(p->dev);
 		ent.push_back(GroupEntry{blocks, f, c, h.iterations, pose_in[i], targets[i], pose_out[i]});
-		blocks += (c + h.spw - 1) / h.spw;
+		blocks += (int)sl.blocks;
 	}
 	if (ent.empty()) return MBIK_OK;
 	if (hipMemcpyAsync(g->d_plans.as<void>(), dp.data(), sizeof(DevPlan) * dp.size(), hipMemcpyHostToDevice, stream) != hipSuccess ||
@@ -1065,7 +1132,9 @@ int32_t mbik_describe_step_classes(const mbik_skeleton_desc *desc, const mbik_co
 	std::string err = mbik::build_topology(*desc, *config, h);
 	if (!err.empty()) return fail(MBIK_EINVAL, err);
 	h.N = 1;
-	mbik::build_schedule(h, std::max(0, lanes_per_skeleton), 1);
+	mbik::LayoutRequest rq;
+	rq.lanes = std::max(0, lanes_per_skeleton);
+	mbik::build_schedule(h, rq, 1);
 	return step_classes_of(h, row_steps, row_cap, classes, class_cap);
 }
 
@@ -1084,7 +1153,7 @@ int32_t mbik_solve_host(mbik_plan *p, int32_t first, int32_t count, const float 
 			(h.P > 0 && hipMemcpy(d_tg, targets, need * h.P * 12 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))
 		return fail(MBIK_EHIP, "hipMemcpy H2D");
 	if (int rc = take_helper_timeout(p)) return rc;
-	int rc = launch(p, first, count, d_in, d_tg, d_out, nullptr, h.iterations, 0, h.NS - 1);
+	int rc = launch(p, full_solve(p, first, count, d_in, d_tg, d_out, nullptr));
 	if (rc) return rc;
 	if (hipMemcpy(pose_out, d_out, need * h.B * 10 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
 		return fail(MBIK_EHIP, std::string("hipMemcpy D2H / kernel: ") + hipGetErrorString(hipGetLastError()));
@@ -1102,16 +1171,16 @@ extern "C" int mbik_debug_replay(mbik_plan *p, int32_t mode, int32_t first, int3
 	if (mode == 0) {
 		p->rec_dump.reset();
 		p->dev.rec_dump = nullptr;
-		p->dev.replay = 0;
 		return MBIK_OK;
 	}
 	int rc = ensure_schedule(p, count);
 	if (rc) return rc;
-	if (!helper_on(p)) return fail(MBIK_EINVAL, "replay needs a helper-wave layout");
+	SolveLaunch sl;
+	if (resolve_launch(p, count, sl, mode) != MBIK_OK || !sl.helper) return fail(MBIK_EINVAL, "replay needs a helper-wave layout");
 	const mbik::HostPlan &h = p->host;
 	int per_iter = 0;
 	for (int r = 0; r < h.nrows; r++) per_iter += mbik::row_max_steps(h, r);
-	const size_t blocks = (size_t)(count + h.spw - 1) / h.spw;
+	const size_t blocks = sl.blocks;
 	if (mode == 1) {
 		p->rec_dump.reset();
 		p->dev.rec_dump = nullptr;
@@ -1119,10 +1188,9 @@ extern "C" int mbik_debug_replay(mbik_plan *p, int32_t mode, int32_t first, int3
 		if ((rc = p->rec_dump.reserve(blocks * p->dev.rec_per_block * kHelpF4 * 64 * sizeof(float4), "replay buffer")) != MBIK_OK) return rc;
 		p->dev.rec_dump = p->rec_dump.as<float4>();
 	}
-	p->dev.replay = mode;
-	rc = launch(p, first, count, pose_in, targets, pose_out, (hipStream_t)stream, h.iterations, 0, h.NS - 1);
-	p->dev.replay = 0;
-	return rc;
+	LaunchArgs a = full_solve(p, first, count, pose_in, targets, pose_out, (hipStream_t)stream);
+	a.replay = mode;
+	return launch(p, a);
 }
 #endif
 

@@ -693,8 +693,13 @@ int step_class_at(const HostPlan &p, int row, int q) {
 	return (p.step_class[p.step_class[row] + (q >> 2)] >> (8 * (q & 3))) & 0xff;
 }
 
-void build_schedule(HostPlan &p, int32_t lanes, int64_t nlaunch, int32_t spw_override, int32_t interval_override,
-		BlocksPerCU blocks_per_cu, void *ctx, int cus) {
+void build_schedule(HostPlan &p, const LayoutRequest &rq, int64_t nlaunch, BlocksPerCU blocks_per_cu, void *ctx, int cus) {
+	const int32_t lanes = rq.lanes, spw_override = rq.spw, interval_override = rq.interval;
+	p.staging = rq.staging;
+	p.state_hbm = rq.state_hbm;
+	p.waves_per_simd = rq.waves_per_simd;
+	p.wave_roles = rq.wave_roles;
+	p.cm_roles = rq.cm_roles;
 	p.seg_eff_lcp.assign(p.seg_effs.size() + 1, 0);
 	p.seg_eff_grp.assign(p.seg_effs.size() + 1, 0);
 	for (int sg = 0; sg < p.NS; sg++)

@@ -149,6 +149,9 @@ struct HostPlan {
 	std::vector<int32_t> cm_pre, cm_sub;
 	int32_t cm_maxd = 1, cm_npos = 0;
 	// ---- launch shape ----
+	// Resolved by build_schedule from a LayoutRequest, and assigned by nothing else: from here to
+	// nrows, every field is what the last build_schedule call left (kernel selection, the launch
+	// and mbik_plan_get_info read them).
 	int32_t K = 4, log2K = 2, spw = 16;
 	int64_t lds_block_bytes = 0;
 	// Heading staging of multi-effector segments: split the heading work over the segment's
@@ -251,13 +254,22 @@ std::string build_skeletons(HostPlan &plan, int32_t n, const float *setup_pose, 
 void setup_tables(HostPlan &plan);
 struct SetupView;
 SetupView setup_view(const HostPlan &plan, int32_t n, int32_t max_cones_in);
-// Chooses lanes-per-skeleton / skeletons-per-block and the sibling-level schedule.
-// spw_override / interval_override: 0 = automatic (mbik_plan_set_layout).
+// Everything build_schedule is asked for; the defaults are a HostPlan's own.  The last five are
+// copied into the HostPlan fields of the same names (HostPlan documents them).
+struct LayoutRequest {
+	int32_t lanes = 0, spw = 0, interval = 0; // lanes per skeleton, skeletons per block, checkpoint interval: 0 = automatic
+	int staging = 1;
+	int32_t state_hbm = 0;
+	int32_t waves_per_simd = 1;
+	int32_t wave_roles = 0, cm_roles = 0;
+};
+// Chooses lanes-per-skeleton / skeletons-per-block and the sibling-level schedule, and writes
+// the plan's launch-shape fields; of the layout it reads the request only.
 // blocks_per_cu(lds_bytes): how many one-wave blocks of that LDS size a CU holds at once
 // (the device's occupancy query); nullptr = LDS-only estimate.  cus: compute units.
 using BlocksPerCU = int (*)(void *ctx, int64_t lds_bytes);
-void build_schedule(HostPlan &plan, int32_t lanes_per_skeleton, int64_t skeletons_in_launch, int32_t spw_override = 0,
-		int32_t interval_override = 0, BlocksPerCU blocks_per_cu = nullptr, void *ctx = nullptr, int cus = 256);
+void build_schedule(HostPlan &plan, const LayoutRequest &request, int64_t skeletons_in_launch, BlocksPerCU blocks_per_cu = nullptr,
+		void *ctx = nullptr, int cus = 256);
 // LDS floats per skeleton used by the kernel: L (12 per bone), G (12 per checkpoint), targets + stale cache
 // (12 + 12 per pin), stale flags (1 per pin), the staged-heading area (hs_floats), and with
 // stabilization the pre-loop target

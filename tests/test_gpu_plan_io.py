@@ -33,6 +33,27 @@ def test_loaded_plan_solves_bitwise(oracle, mbik, cfg, n):
     assert b.save() == data
 
 
+def test_plan_file_of_an_earlier_build_loads(oracle, mbik):
+    """tests/golden/plan_c1_n2_parent.bin: C1 x 2 (first=7) with set_layout(0, 3, 2) and heading
+    staging 0, saved by the library as it was before the launch layout was gathered in one
+    place.  It loads, reports that layout, saves byte-identically and solves like a new plan."""
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_c1_n2_parent.bin"), "rb") as f:
+        data = f.read()
+    wl = W.generate(1, 2, first=7)
+    b = Plan.load(data)
+    assert b.save() == data
+    a = Plan.from_workload(wl)
+    a.set_layout(0, 3, 2)
+    a.set_heading_staging(0)
+    assert a.save() == data
+    got = b.solve_host(wl.pose, wl.targets)
+    assert np.array_equal(got.view(np.uint32), a.solve_host(wl.pose, wl.targets).view(np.uint32))
+    assert b.info() == a.info()
+    assert (b.info()["checkpoint_interval"], b.info()["heading_staging"]) == (2, 0)
+    assert_parity(got, oracle.Oracle(wl).solve(wl.pose, wl.targets, threads=8), "C1 plan file of an earlier build")
+
+
 def test_table_addressing_override_survives(oracle, mbik):
     """mbik_plan_set_table_addressing(1) is one of the saved layout overrides (format 2): the
     loaded plan still runs the 64-bit-index kernel -- bitwise like the original -- and so still
