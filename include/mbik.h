@@ -24,6 +24,8 @@
  *   mbik_clip_sample   <- Animation::position_track_interpolate / rotation_track_interpolate /
  *                         scale_track_interpolate for every bone: the animation that writes the poses
  *                         a SkeletonModifier3D receives (Godot 4.3 core)
+ *   mbik_clip_sample_layers <- AnimationMixer::_blend_process / _blend_apply: the blend of several
+ *                         animations, each with its own time and weight (Godot 4.3 core)
  *   mbik_plan_destroy  <- ~ManyBoneIK3D / set_dirty() rebuild
  *   mbik_last_error    <- ERR_FAIL_* messages (the reference prints and returns)
  *
@@ -465,9 +467,9 @@ int32_t mbik_pose_blend_cpu(int32_t bone_count, int32_t libm_variant, int32_t co
  *   6. A NaN produced by the arithmetic of 5 is stored as 0x7fc00000; copied bits stay as they are.
  * mbik_clip_sample_cpu gives the same bits from the same code.  Deviations from Godot: _find treats
  * a time within is_equal_approx of a key as that key, here the compare is exact; cubic
- * interpolation, ping-pong, backward playback, key transitions (ease) and AnimationMixer's blend of
- * several animations are not covered -- two mbik_clip_sample calls and mbik_pose_blend with a
- * per-skeleton weight give a cross-fade. */
+ * interpolation, ping-pong, backward playback and key transitions (ease) are not covered.
+ * AnimationMixer's blend of several animations is mbik_clip_sample_layers, below (mbik_pose_blend is
+ * the modifier's `influence`, a different function). */
 typedef struct mbik_clip_track {
 	int32_t bone;            /* [0, bone_count) */
 	int32_t channel;         /* 0 position (3 floats a key), 1 rotation (4: x,y,z,w), 2 scale (3) */
@@ -500,6 +502,74 @@ int32_t mbik_clip_sample(mbik_clipset *set, int32_t count, const double *time /*
  * mbik_clipset_create's and mbik_clip_sample's checks. */
 int32_t mbik_clip_sample_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
 		int32_t libm_variant, int32_t count, const double *time, const int32_t *clip_index, int32_t clip, float *pose_out);
+
+/* Layered clip sampling: AnimationMixer's blend of several animations, in one call and one kernel.
+ * Characters of a crowd cross-fade walk into run and carry partial-weight layers; each skeleton
+ * has layer_count records (time, clip, weight), and the call writes the blend of their samples.
+ * Purely additive to ABI 15: two new symbols and one new struct, no existing struct or call
+ * changed, MBIK_ABI_VERSION stays 15.  A caller detects the feature by the presence of the symbol
+ * mbik_clip_sample_layers (dlsym, or MBIK_CLIP_MAX_LAYERS at compile time).
+ *
+ * Semantics -- Godot's core is not part of the reference tree, so mbik_clip_sample_layers_cpu is
+ * the specification, modelled on Godot 4.3's AnimationMixer::_blend_init / _blend_calc_total_weight
+ * / _blend_process / _blend_apply: every layer's offset from the rest pose is accumulated,
+ * loc += (x - init) * blend and rot = (rot * slerp(identity, init^-1 * x, blend)).normalized().
+ * Without MBIK_CLIP_LAYERS_NORMALIZE the mode is the mixer's deterministic one (blend = weight);
+ * with it the non-deterministic one, which is AnimationPlayer's cross-fade (blend = weight / the
+ * channel's total weight).  All arithmetic is float32 and unfused, in the order written.  For
+ * skeleton s, bone b and channel ch (position, rotation, scale), I = the rest pose's value of that
+ * channel (init_loc / init_rot / init_scale), K = layer_count:
+ *   1. For l = 0 .. K-1: a layer with clip == -1 is off -- nothing of it is read, its time and
+ *      weight may be anything.  Any other clip outside [0, clip_count) makes the whole skeleton
+ *      invalid: every float of it is 0x7fc00000 and no table is read (mbik_clip_sample's step 1).
+ *      The kernel makes this test itself, before any table access.
+ *   2. w = weight; if (w < 0) w = 0; if (w > 1) w = 1.  A NaN passes both compares and propagates.
+ *   3. A layer that is on contributes to (b, ch) when its clip tracks that channel (at least one
+ *      key).  Other layers do not exist for that channel.
+ *   4. Without the flag blend_l = w_l.  With it: total = 0.0f, total = total + w_l over the
+ *      contributing layers, ascending; |total| < CMP_EPSILON (1e-5): the channel receives nothing
+ *      (step 6); otherwise blend_l = w_l / total (IEEE float division).
+ *   5. acc = I.  For each contributing layer, ascending: |blend_l| < CMP_EPSILON (false for NaN):
+ *      the layer is skipped and none of its keys is read (Godot's is_zero_approx(blend)).
+ *      Otherwise x = the channel's value exactly as mbik_clip_sample's steps 2 to 6 give it for
+ *      (time_l, clip_l), 0x7fc00000 for a non-finite time included, and
+ *        position, scale:  acc = acc + (x - I) * blend_l   (V3 - V3, V3 * float, V3 + V3)
+ *        rotation:         d = inverse(I) * x  (conjugate; Quaternion::operator*),
+ *                          e = slerp(identity, d, blend_l)  (Quaternion::slerp as in mbik_pose_blend),
+ *                          acc = normalized(acc * e).
+ *   6. A channel that had at least one layer accumulated stores acc, any NaN as 0x7fc00000.  Every
+ *      other channel -- untracked, all layers off or skipped, a zero total -- stores the rest
+ *      pose's bits, copied.
+ * Consequences: with K = 1 and w = 1 the result is I + (x - I) * 1 and normalized(I * (I^-1 * x)),
+ * Godot's behaviour; it is not the bits of mbik_clip_sample.  Quaternions are used as given:
+ * neither the rest pose nor the keys are renormalised on input.
+ * Deviations from Godot: step 2's clamp (Godot would extrapolate; the slerp's double sine needs its
+ * argument in [0, pi/2], the reason mbik_pose_blend gives for clamping negative weights; additive
+ * layers are out of scope).  init_* are the rest pose's ten floats as given (Godot derives them
+ * from the rest Transform3D).  Per-track blend weights (filters), root motion, RESET animations
+ * and post_process_key_value are not covered.
+ *
+ * MBIK_EINVAL: a null set; count < 0; layer_count outside [1, MBIK_CLIP_MAX_LAYERS]; unknown flag
+ * bits; and, when there is work to do, a null layers or pose_out, layers not 8-byte aligned, or
+ * pose_out overlapping layers.  count == 0 or a set without bones returns MBIK_OK without a launch.
+ * Device buffers on the set's device, asynchronous on hip_stream; layers is read by the kernel
+ * only, never by the host.  layers needs 8-byte alignment (a 16-byte aligned array moves one load
+ * a record), pose_out float alignment; element offsets are 64-bit; mbik_clip_sample's limit of
+ * 2^39 bones a call applies. */
+typedef struct mbik_clip_layer {
+	double time;             /* seconds, as mbik_clip_sample's time[s] */
+	int32_t clip;            /* [0, clip_count), or -1: the layer is off */
+	float weight;            /* clamped into [0, 1] */
+} mbik_clip_layer;           /* 16 bytes */
+#define MBIK_CLIP_MAX_LAYERS 8
+#define MBIK_CLIP_LAYERS_NORMALIZE 1u
+int32_t mbik_clip_sample_layers(mbik_clipset *set, int32_t count, int32_t layer_count,
+		const mbik_clip_layer *layers /* device [count][layer_count] */, uint32_t flags,
+		float *pose_out /* device [count][bones][10] */, void *hip_stream);
+/* Host-only (no device needed): the same arithmetic from the same code on host buffers, with
+ * mbik_clipset_create's and mbik_clip_sample_layers' checks. */
+int32_t mbik_clip_sample_layers_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		int32_t libm_variant, int32_t count, int32_t layer_count, const mbik_clip_layer *layers, uint32_t flags, float *pose_out);
 
 /* Linear blend skinning of a mesh from skin transforms (ABI 10): what mbik_pose_globals' skinned
  * output exists for, on the device and on the stream of the solve.  The semantics are those of

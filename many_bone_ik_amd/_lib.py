@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = (
     "mbik_solve", "mbik_solve_checked", "mbik_solve_host", "mbik_segment_solve", "mbik_plan_segment_table", "mbik_describe_topology",
     "mbik_plan_step_classes", "mbik_describe_step_classes",
     "mbik_group_create", "mbik_group_solve", "mbik_group_destroy", "mbik_multi_create", "mbik_multi_solve",
-    "mbik_multi_skeletons", "mbik_multi_destroy", "mbik_capture_targets", "mbik_pose_globals", "mbik_pose_globals_cpu", "mbik_pose_blend", "mbik_pose_blend_cpu", "mbik_clipset_create", "mbik_clipset_destroy", "mbik_clip_sample", "mbik_clip_sample_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
+    "mbik_multi_skeletons", "mbik_multi_destroy", "mbik_capture_targets", "mbik_pose_globals", "mbik_pose_globals_cpu", "mbik_pose_blend", "mbik_pose_blend_cpu", "mbik_clipset_create", "mbik_clipset_destroy", "mbik_clip_sample", "mbik_clip_sample_cpu", "mbik_clip_sample_layers", "mbik_clip_sample_layers_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
     "mbik_skin_vertices", "mbik_skin_vertices_cpu", "mbik_mesh_launch_shape", "mbik_mesh_create_shaped", "mbik_skin_vertices_shaped",
     "mbik_skin_vertices_shaped_cpu", "mbik_mesh_bone_boxes", "mbik_bone_boxes_cpu", "mbik_skin_bounds", "mbik_skin_bounds_cpu",
     "mbik_cull_boxes", "mbik_cull_boxes_cpu", "mbik_skin_vertices_listed", "mbik_skin_vertices_listed_cpu", "mbik_selftest_math",
@@ -90,6 +90,15 @@ class MbikClipTrack(C.Structure):
 class MbikClipDesc(C.Structure):
     _fields_ = [("length", C.c_double), ("loop_mode", C.c_int32), ("track_count", C.c_int32),
                 ("tracks", C.POINTER(MbikClipTrack))]
+
+
+class MbikClipLayer(C.Structure):
+    _fields_ = [("time", C.c_double), ("clip", C.c_int32), ("weight", C.c_float)]
+
+
+# mbik_clip_sample_layers: the most layers a skeleton can have, and its flag
+CLIP_MAX_LAYERS = 8
+CLIP_LAYERS_NORMALIZE = 1
 
 
 class MbikMeshShapes(C.Structure):
@@ -246,6 +255,11 @@ def load():
     L.mbik_clip_sample.restype = C.c_int32
     L.mbik_clip_sample_cpu.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MbikClipDesc), C.c_int32, C.c_int32, vp, vp, C.c_int32, vp]
     L.mbik_clip_sample_cpu.restype = C.c_int32
+    L.mbik_clip_sample_layers.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_uint32, vp, vp]
+    L.mbik_clip_sample_layers.restype = C.c_int32
+    L.mbik_clip_sample_layers_cpu.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MbikClipDesc), C.c_int32, C.c_int32, C.c_int32, vp,
+                                              C.c_uint32, vp]
+    L.mbik_clip_sample_layers_cpu.restype = C.c_int32
     L.mbik_mesh_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.POINTER(vp)]
     L.mbik_mesh_create.restype = C.c_int32
     L.mbik_mesh_destroy.argtypes = [vp]

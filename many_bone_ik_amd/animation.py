@@ -5,6 +5,9 @@ count and a libm_variant.  `ClipSet.sample()` takes device pointers -- one time 
 clip index (int32) per skeleton -- and writes the poses `Plan.solve()` reads; it is asynchronous on
 the given HIP stream.  `clip_sample_cpu()` runs the same code on numpy arrays without a device, and
 `synthetic_clips()` is the seeded clip generator the tests and tools/clip_bench.py use.
+`ClipSet.sample_layers()` blends up to MAX_LAYERS (time, clip, weight) records a skeleton
+(`pack_layers()`, LAYER_DTYPE) as Godot's AnimationMixer does; `clip_sample_layers_cpu()` is its
+host form.
 
 A clip is a dict: {"length": seconds, "loop_mode": 0 none | 1 linear, "tracks": [track, ...]}; a
 track is a dict: {"bone", "channel": 0 position | 1 rotation | 2 scale, "interpolation": 0 nearest |
@@ -24,6 +27,11 @@ NEAREST, LINEAR = 0, 1
 LOOP_NONE, LOOP_LINEAR = 0, 1
 # floats of a pose record [10] that a channel owns (quaternion xyzw | position | scale)
 CHANNEL_SLICE = {POSITION: slice(4, 7), ROTATION: slice(0, 4), SCALE: slice(7, 10)}
+# mbik_clip_layer: one (time, clip, weight) record of mbik_clip_sample_layers, 16 bytes
+LAYER_DTYPE = np.dtype([("time", "<f8"), ("clip", "<i4"), ("weight", "<f4")])
+MAX_LAYERS = _lib.CLIP_MAX_LAYERS
+LAYERS_NORMALIZE = _lib.CLIP_LAYERS_NORMALIZE
+LAYER_OFF = -1
 
 
 def _ptr(a):
@@ -80,6 +88,13 @@ class ClipSet:
         check(self._L.mbik_clip_sample(self.h, count, C.c_void_p(time_ptr or None), C.c_void_p(clip_index_ptr or None), clip,
                                        C.c_void_p(pose_out_ptr or None), C.c_void_p(stream or None)))
 
+    def sample_layers(self, layers_ptr: int, pose_out_ptr: int, count: int, layer_count: int, flags: int = 0, stream: int = 0) -> None:
+        """mbik_clip_sample_layers: pose_out [count][bones][10] from the device array layers
+        [count][layer_count] of LAYER_DTYPE records, blended as AnimationMixer blends them (flags:
+        LAYERS_NORMALIZE for AnimationPlayer's cross-fade); asynchronous on `stream`."""
+        check(self._L.mbik_clip_sample_layers(self.h, count, layer_count, C.c_void_p(layers_ptr or None), flags,
+                                              C.c_void_p(pose_out_ptr or None), C.c_void_p(stream or None)))
+
     def close(self) -> None:
         if getattr(self, "h", None):
             self._L.mbik_clipset_destroy(self.h)
@@ -110,6 +125,35 @@ def clip_sample_cpu(bone_count: int, rest_pose, clips, time, clip_index=None, cl
     out = np.empty((t.shape[0], bone_count, 10), np.float32)
     check(L.mbik_clip_sample_cpu(bone_count, _ptr(rest), len(clips), descs, libm_variant, t.shape[0], _ptr(t), _ptr(idx), clip,
                                  _ptr(out)))
+    del keep
+    return out
+
+
+def pack_layers(time, clip, weight):
+    """Layer records [count][K] of LAYER_DTYPE from three arrays of that shape (a 1-D array is one
+    layer a skeleton).  clip == LAYER_OFF switches a layer off."""
+    t = np.asarray(time, np.float64)
+    if t.ndim == 1:
+        t = t[:, None]
+    assert t.ndim == 2, t.shape
+    out = np.empty(t.shape, LAYER_DTYPE)
+    out["time"] = t
+    out["clip"] = np.asarray(clip, np.int32).reshape(t.shape)
+    out["weight"] = np.asarray(weight, np.float32).reshape(t.shape)
+    return out
+
+
+def clip_sample_layers_cpu(bone_count: int, rest_pose, clips, layers, flags: int = 0, libm_variant: int = 0):
+    """mbik_clip_sample_layers_cpu (host only): `layers` [count][K] of LAYER_DTYPE (pack_layers) ->
+    poses [count][bones][10]."""
+    L = _lib.load()
+    rest = _rest(bone_count, rest_pose)
+    descs, keep = _descs(clips)
+    rec = np.ascontiguousarray(layers, LAYER_DTYPE)
+    assert rec.ndim == 2, rec.shape
+    out = np.empty((rec.shape[0], bone_count, 10), np.float32)
+    check(L.mbik_clip_sample_layers_cpu(bone_count, _ptr(rest), len(clips), descs, libm_variant, rec.shape[0], rec.shape[1], _ptr(rec),
+                                        flags, _ptr(out)))
     del keep
     return out
 

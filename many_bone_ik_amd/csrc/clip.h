@@ -6,6 +6,7 @@
 // One code path for both sides, made of IEEE-exact operations only (double compares, differences
 // and sums, an integer fmod, gd_math.h's float arithmetic and blend.h's slerp), so the device and
 // the host produce the same bits.  include/mbik.h (ABI 12) states the semantics; DESIGN.md §16.
+// clip_layers.h blends several such samples a skeleton (mbik_clip_sample_layers).
 #pragma once
 
 #include <cstdint>
@@ -154,37 +155,36 @@ GDI float clip_nan() {
 	return c.f;
 }
 
-// A position or scale channel into out[0..2] from its loaded keys.  rest: the rest pose's three floats.
-GDI void clip_store_vec(const ClipChan &ch, const ClipPick &p, float c, const ClipValue &a, const ClipValue &b, const float *rest,
-		float *out) {
-	if (ch.n == 0) {
-		out[0] = rest[0], out[1] = rest[1], out[2] = rest[2];
-	} else if (p.mode == kClipCopy) {
-		out[0] = a.x, out[1] = a.y, out[2] = a.z;
-	} else {
-		const V3 r = v3(a.x, a.y, a.z) + (v3(b.x, b.y, b.z) - v3(a.x, a.y, a.z)) * c; // Vector3::lerp
-		out[0] = blend_canon(r.x), out[1] = blend_canon(r.y), out[2] = blend_canon(r.z);
-	}
+// A tracked position or scale channel from its loaded keys.
+GDI V3 clip_value_vec(const ClipPick &p, float c, const ClipValue &a, const ClipValue &b) {
+	if (p.mode == kClipCopy) return v3(a.x, a.y, a.z);
+	const V3 r = v3(a.x, a.y, a.z) + (v3(b.x, b.y, b.z) - v3(a.x, a.y, a.z)) * c; // Vector3::lerp
+	return v3(blend_canon(r.x), blend_canon(r.y), blend_canon(r.z));
 }
 
-// One bone of one skeleton: out10 = the pose (quaternion xyzw, position, scale) of `bone` at raw
-// time t in clip `clip`.  What a lane waits for is memory, so the loads are arranged in as few
-// dependent rounds as the data allows: the clip's length and the three headers; the search steps,
-// three loads each; then the two key times and the two key values of all three channels at once.
-GDI void clip_sample_bone(const ClipView &v, int clip, int bone, double t, int lv, float *out10) {
-	if (clip < 0 || clip >= v.clip_count) {
-		for (int f = 0; f < 10; f++) out10[f] = clip_nan();
-		return;
-	}
-	const ClipInfo info = v.clips[clip];
-	const ClipHeader *h = v.headers + ((int64_t)clip * v.B + bone) * 3;
-	ClipChan pos = clip_chan(v, h[0]), rot = clip_chan(v, h[1]), scl = clip_chan(v, h[2]);
-	const float *rest = v.rest + (int64_t)bone * 10;
+// The three channels of one bone at one time in one clip, before they become a pose: steps 2 to 6
+// of mbik_clip_sample for the channels that have keys.  has_* is false for a channel without keys,
+// whose value is then unspecified (step 4 belongs to the caller: clip_sample_bone stores the rest
+// pose, clip_layers.h leaves the channel out of the blend).
+struct ClipSampled {
+	Q rot;
+	V3 pos, scl;
+	bool has_pos, has_rot, has_scl;
+};
+// hp / hr / hs: the bone's three headers in `info`'s clip, already loaded -- a caller that samples
+// several clips loads the next one's while this one's keys are searched.  What a lane waits for is
+// memory, so the loads are arranged in as few dependent rounds as the data allows: the search
+// steps, three loads each; then the two key times and the two key values of all three channels at
+// once.
+GDI ClipSampled clip_sample_channels(const ClipView &v, const ClipInfo &info, const ClipHeader &hp, const ClipHeader &hr,
+		const ClipHeader &hs, double t, int lv) {
+	ClipChan pos = clip_chan(v, hp), rot = clip_chan(v, hr), scl = clip_chan(v, hs);
+	ClipSampled out;
+	out.has_pos = pos.n != 0, out.has_rot = rot.n != 0, out.has_scl = scl.n != 0;
 	if (!clip_finite(t)) { // no key is read
-		for (int f = 0; f < 4; f++) out10[f] = rot.n ? clip_nan() : rest[f];
-		for (int f = 4; f < 7; f++) out10[f] = pos.n ? clip_nan() : rest[f];
-		for (int f = 7; f < 10; f++) out10[f] = scl.n ? clip_nan() : rest[f];
-		return;
+		const float nan = clip_nan();
+		out.rot = q4(nan, nan, nan, nan), out.pos = v3(nan, nan, nan), out.scl = v3(nan, nan, nan);
+		return out;
 	}
 	const double tp = clip_time(t, info.length, info.loop_mode);
 	const int nrs = rot.n > scl.n ? rot.n : scl.n, nmax = pos.n > nrs ? pos.n : nrs;
@@ -197,17 +197,33 @@ GDI void clip_sample_bone(const ClipView &v, int clip, int bone, double t, int l
 	const ClipValue pVa = pos.V[pp.a], pVb = pos.V[pp.b], rVa = rot.V[pr.a], rVb = rot.V[pr.b], sVa = scl.V[ps.a], sVb = scl.V[ps.b];
 	const float pc = clip_weight(pp.mode, pTa, pTb, tp, info.length), rc = clip_weight(pr.mode, rTa, rTb, tp, info.length),
 				sc = clip_weight(ps.mode, sTa, sTb, tp, info.length);
-	if (rot.n == 0) {
-		out10[0] = rest[0], out10[1] = rest[1], out10[2] = rest[2], out10[3] = rest[3];
-	} else if (pr.mode == kClipCopy) {
-		out10[0] = rVa.x, out10[1] = rVa.y, out10[2] = rVa.z, out10[3] = rVa.w;
+	if (rot.n == 0 || pr.mode == kClipCopy) {
+		out.rot = q4(rVa.x, rVa.y, rVa.z, rVa.w);
 	} else {
 		// Quaternion::slerp, not renormalised; a wave none of whose lanes gets here skips it
 		const Q r = blend_slerp(q4(rVa.x, rVa.y, rVa.z, rVa.w), q4(rVb.x, rVb.y, rVb.z, rVb.w), rc, lv);
-		out10[0] = blend_canon(r.x), out10[1] = blend_canon(r.y), out10[2] = blend_canon(r.z), out10[3] = blend_canon(r.w);
+		out.rot = q4(blend_canon(r.x), blend_canon(r.y), blend_canon(r.z), blend_canon(r.w));
 	}
-	clip_store_vec(pos, pp, pc, pVa, pVb, rest + 4, out10 + 4);
-	clip_store_vec(scl, ps, sc, sVa, sVb, rest + 7, out10 + 7);
+	out.pos = clip_value_vec(pp, pc, pVa, pVb);
+	out.scl = clip_value_vec(ps, sc, sVa, sVb);
+	return out;
+}
+
+// One bone of one skeleton: out10 = the pose (quaternion xyzw, position, scale) of `bone` at raw
+// time t in clip `clip`: the sampled channels, and the rest pose's bits where a channel has no keys.
+GDI void clip_sample_bone(const ClipView &v, int clip, int bone, double t, int lv, float *out10) {
+	if (clip < 0 || clip >= v.clip_count) {
+		for (int f = 0; f < 10; f++) out10[f] = clip_nan();
+		return;
+	}
+	const ClipInfo info = v.clips[clip];
+	const ClipHeader *h = v.headers + ((int64_t)clip * v.B + bone) * 3;
+	const float *rest = v.rest + (int64_t)bone * 10;
+	const ClipSampled s = clip_sample_channels(v, info, h[0], h[1], h[2], t, lv);
+	out10[0] = s.has_rot ? s.rot.x : rest[0], out10[1] = s.has_rot ? s.rot.y : rest[1];
+	out10[2] = s.has_rot ? s.rot.z : rest[2], out10[3] = s.has_rot ? s.rot.w : rest[3];
+	out10[4] = s.has_pos ? s.pos.x : rest[4], out10[5] = s.has_pos ? s.pos.y : rest[5], out10[6] = s.has_pos ? s.pos.z : rest[6];
+	out10[7] = s.has_scl ? s.scl.x : rest[7], out10[8] = s.has_scl ? s.scl.y : rest[8], out10[9] = s.has_scl ? s.scl.z : rest[9];
 }
 
 } // namespace mbik

@@ -2,11 +2,14 @@
 // launches k_clip.hip's kernel on the set's device, and mbik_clip_sample_cpu, which runs the same
 // per-bone code (clip.h) on the host.  The front stage of a frame: the poses mbik_solve reads are
 // sampled on the solve's stream from a time and a clip index per skeleton.  DESIGN.md §16.
+// mbik_clip_sample_layers and its _cpu form blend up to 8 (time, clip, weight) layers a skeleton
+// the same way (k_clip_layers.hip, clip_layers.h).
 #include "host.h"
 
 #include <cmath>
+#include <cstddef>
 
-#include "clip.h"
+#include "clip_layers.h"
 
 using namespace mbik_host;
 
@@ -95,6 +98,24 @@ int check_call(int32_t B, int32_t clip_count, int32_t count, const double *time,
 	return 0;
 }
 
+// The same for a layered call; the records themselves are the kernel's (or the per-bone code's) to test.
+int check_layers_call(int32_t B, int32_t count, int32_t layer_count, const mbik_clip_layer *layers, uint32_t flags, const float *pose_out) {
+	if (count < 0) return fail(MBIK_EINVAL, "negative count");
+	if (layer_count < 1 || layer_count > MBIK_CLIP_MAX_LAYERS)
+		return fail(MBIK_EINVAL, "layer_count " + std::to_string(layer_count) + " outside [1, " + std::to_string(MBIK_CLIP_MAX_LAYERS) + "]");
+	if (flags & ~MBIK_CLIP_LAYERS_NORMALIZE) return fail(MBIK_EINVAL, "unknown flags " + std::to_string(flags));
+	if (count == 0 || B == 0) return 1;
+	if (!layers) return fail(MBIK_EINVAL, "null layers");
+	if (!pose_out) return fail(MBIK_EINVAL, "null pose_out");
+	if (reinterpret_cast<uintptr_t>(layers) % 8) return fail(MBIK_EINVAL, "layers is not 8-byte aligned");
+	if (overlap(layers, (size_t)count * layer_count * sizeof(mbik_clip_layer), pose_out, (size_t)count * B * 10 * sizeof(float)))
+		return fail(MBIK_EINVAL, "pose_out overlaps layers");
+	return 0;
+}
+static_assert(sizeof(mbik_clip_layer) == sizeof(mbik::ClipLayer) && offsetof(mbik_clip_layer, clip) == offsetof(mbik::ClipLayer, clip) &&
+				offsetof(mbik_clip_layer, weight) == offsetof(mbik::ClipLayer, weight),
+		"mbik_clip_layer is clip_layers.h's ClipLayer");
+
 size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 } // namespace
@@ -159,6 +180,33 @@ int32_t mbik_clip_sample_cpu(int32_t bone_count, const float *rest_pose, int32_t
 		const int32_t c = clip_index ? clip_index[s] : clip;
 		for (int32_t b = 0; b < bone_count; b++) mbik::clip_sample_bone(v, c, b, time[s], libm_variant, pose_out + (s * bone_count + b) * 10);
 	}
+	return MBIK_OK;
+}
+
+int32_t mbik_clip_sample_layers(mbik_clipset *s, int32_t count, int32_t layer_count, const mbik_clip_layer *layers, uint32_t flags,
+		float *pose_out, void *hip_stream) {
+	if (!s) return fail(MBIK_EINVAL, "null clip set");
+	const int rc = check_layers_call(s->B, count, layer_count, layers, flags, pose_out);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	if ((int64_t)count * s->B > (int64_t)INT32_MAX * 256) return fail(MBIK_EUNSUPPORTED, "more than 2^39 bones in one call");
+	DeviceGuard guard(s->device);
+	hipError_t e = mbik::launch_clip_layers(reinterpret_cast<hipStream_t>(hip_stream), s->view, s->libm, (int64_t)count * s->B,
+			reinterpret_cast<const mbik::ClipLayer *>(layers), layer_count, flags, pose_out);
+	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("layered clip sample launch failed: ") + hipGetErrorString(e));
+	return MBIK_OK;
+}
+
+int32_t mbik_clip_sample_layers_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		int32_t libm_variant, int32_t count, int32_t layer_count, const mbik_clip_layer *layers, uint32_t flags, float *pose_out) {
+	Packed pk;
+	if (int rc = pack(bone_count, rest_pose, clip_count, clips, libm_variant, pk)) return rc;
+	const int rc = check_layers_call(bone_count, count, layer_count, layers, flags, pose_out);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	const mbik::ClipView v = pk.view(bone_count);
+	const mbik::ClipLayer *L = reinterpret_cast<const mbik::ClipLayer *>(layers);
+	for (int64_t s = 0; s < count; s++)
+		for (int32_t b = 0; b < bone_count; b++)
+			mbik::clip_layers_bone(v, L + s * layer_count, layer_count, flags, b, libm_variant, pose_out + (s * bone_count + b) * 10);
 	return MBIK_OK;
 }
 
