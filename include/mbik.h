@@ -775,6 +775,78 @@ int32_t mbik_cull_boxes(mbik_mesh *mesh, int32_t count, const float *boxes, cons
 		int32_t plane_count, const float *planes, uint8_t *visible, int32_t *indices, int32_t *visible_count, void *hip_stream);
 int32_t mbik_cull_boxes_cpu(int32_t count, const float *boxes, const float *skeleton_global, float margin, int32_t plane_count,
 		const float *planes, uint8_t *visible, int32_t *indices, int32_t *visible_count);
+/* 4. Distance LOD lists: one ordered list per visibility range, so that each level of detail of a
+ * character -- a mesh of its own -- skins the skeletons in its distance band and no others
+ * (mbik_skin_vertices_listed takes each list as it is).  Additive: nothing that existed changed,
+ * MBIK_ABI_VERSION stays 15, and a caller detects the feature by the presence of the symbol
+ * mbik_cull_lod (dlsym, or MBIK_LOD_MAX_RANGES at compile time).
+ *
+ * Semantics -- Godot's core is not part of the reference tree, so mbik_cull_lod_cpu is the
+ * specification and the device gives the same bits.  It is modelled on Godot 4.3's
+ * RendererSceneCull::_visibility_range_check with VISIBILITY_RANGE_FADE_DISABLED
+ * (GeometryInstance3D.visibility_range_begin / _end and their margins), placed in front of step 3's
+ * plane test.  A range is mbik_lod_range; a 0 in begin or end means no limit on that side.  For
+ * skeleton s, in this order:
+ *   (p, z) = boxes[s], then skeleton_global and margin, exactly as in 3.; vis = 3.'s verdict for it
+ *   c = p + z * 0.5f                                                         AABB::get_center
+ *   v = c - camera; dist = sqrt((v.x*v.x + v.y*v.y) + v.z*v.z)              Vector3::distance_to
+ *   for each range r ascending: prev = (state[s] >> r) & 1                   in range r last time?
+ *     bo = -begin_margin; eo = end_margin; if (!prev) { bo = -bo; eo = -eo }
+ *     in_r = !(end > 0 && dist > end + eo) && !(begin > 0 && dist < begin + bo)
+ *   state[s] = bit r is in_r for r < range_count, 0 above
+ *   level[s] = the least r with vis && in_r, or MBIK_LOD_NONE
+ * Each sum is one float32 addition.  The margins are the hysteresis: a skeleton that was inside a
+ * range stays until it is a margin past the edge, one that was outside enters only a margin inside
+ * it.  A NaN dist fails both compares, so such a skeleton is in every range: the conservative side,
+ * as in the plane test.  state is written for every skeleton, whatever vis is: the engine runs its
+ * visibility-range pass over all range-carrying instances before the frustum test, and so a skeleton
+ * that comes back into view has the state of where it is, not of where it left.  A caller starts
+ * with zeros for strict entry (a skeleton inside a margin may be in no range for that frame) or with
+ * 0xFF for lenient entry, and keeps the buffer from frame to frame.
+ * List r is indices[r * count + 0 .. n_r), n_r = list_counts[r]:
+ *   without MBIK_LOD_EXCLUSIVE  the s with vis && in_r; ranges may overlap, so a skeleton may be in
+ *                               several lists
+ *   with MBIK_LOD_EXCLUSIVE     the s with level[s] == r: the lists are disjoint
+ * in ascending order, the same list on every run.  list_counts[r] is written by every call (the
+ * caller does not clear it); entries at and past n_r are not touched; the row stride is count and
+ * offsets are 64-bit.  With range_count == 1, ranges[0] all zero and any state, list 0 and its count
+ * are mbik_cull_boxes' indices and visible_count bit for bit.
+ * Deviations from the engine, stated: no fade modes (Godot turns the margins into alpha there), no
+ * visibility_parent dependencies, no per-viewport state, state advances for frustum-culled skeletons
+ * too, and the centre is that of the margin-grown box.
+ * Device buffers on the mesh's device except planes, camera and ranges:
+ *   boxes, skeleton_global, margin, plane_count, planes    as for mbik_cull_boxes
+ *   camera       HOST [3]: the camera's world position
+ *   ranges       HOST [range_count]; planes, camera and ranges are copied at the call into the
+ *                kernels' arguments, so the call stays asynchronous and they may be reused at once
+ *   state        [count] bytes, read and written
+ *   level        [count] bytes, or NULL
+ *   indices      [range_count][count]
+ *   list_counts  [range_count]
+ * Asynchronous on hip_stream.  The mesh gives the device and owns the scratch only (the per-block
+ * counts, shared with mbik_cull_boxes, and one byte a skeleton), so a LOD set passes its first
+ * mesh, and calls on one mesh are stream-ordered; growing the scratch waits for the device.
+ * MBIK_EINVAL: everything mbik_cull_boxes refuses for the arguments the two share (a null mesh,
+ * count < 0, plane_count outside [0, MBIK_CULL_MAX_PLANES], null planes with plane_count > 0, null
+ * boxes with count > 0), range_count outside [1, MBIK_LOD_MAX_RANGES], a null ranges or camera, a
+ * non-finite camera, a range with a non-finite or negative field or with end > 0 && begin > end,
+ * unknown flag bits, with count > 0 a null state, indices or list_counts, any output overlapping an
+ * input or another output (state is both, and may overlap nothing else).  count == 0 writes
+ * range_count zeros to list_counts when given and launches nothing else.  mbik_cull_lod_cpu is the
+ * same on host buffers, without a mesh. */
+typedef struct mbik_lod_range {
+	float begin, end;               /* visibility_range_begin / _end; 0 = no limit on that side */
+	float begin_margin, end_margin; /* visibility_range_begin_margin / _end_margin */
+} mbik_lod_range;                   /* 16 bytes */
+#define MBIK_LOD_MAX_RANGES 8
+#define MBIK_LOD_EXCLUSIVE 1u
+#define MBIK_LOD_NONE 255
+int32_t mbik_cull_lod(mbik_mesh *mesh, int32_t count, const float *boxes, const float *skeleton_global, float margin,
+		int32_t plane_count, const float *planes, const float *camera, int32_t range_count, const mbik_lod_range *ranges,
+		uint32_t flags, uint8_t *state, uint8_t *level, int32_t *indices, int32_t *list_counts, void *hip_stream);
+int32_t mbik_cull_lod_cpu(int32_t count, const float *boxes, const float *skeleton_global, float margin, int32_t plane_count,
+		const float *planes, const float *camera, int32_t range_count, const mbik_lod_range *ranges, uint32_t flags, uint8_t *state,
+		uint8_t *level, int32_t *indices, int32_t *list_counts);
 
 /* List-driven skinning (ABI 15): the skeletons a device-resident list names -- mbik_cull_boxes'
  * indices and visible_count on the same stream are such a list -- skinned without a host read-back

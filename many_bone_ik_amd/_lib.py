@@ -38,7 +38,7 @@ EXPORTED_SYMBOLS = (
     "mbik_multi_skeletons", "mbik_multi_destroy", "mbik_capture_targets", "mbik_pose_globals", "mbik_pose_globals_cpu", "mbik_pose_blend", "mbik_pose_blend_cpu", "mbik_clipset_create", "mbik_clipset_destroy", "mbik_clip_sample", "mbik_clip_sample_cpu", "mbik_clip_sample_layers", "mbik_clip_sample_layers_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
     "mbik_skin_vertices", "mbik_skin_vertices_cpu", "mbik_mesh_launch_shape", "mbik_mesh_create_shaped", "mbik_skin_vertices_shaped",
     "mbik_skin_vertices_shaped_cpu", "mbik_mesh_bone_boxes", "mbik_bone_boxes_cpu", "mbik_skin_bounds", "mbik_skin_bounds_cpu",
-    "mbik_cull_boxes", "mbik_cull_boxes_cpu", "mbik_skin_vertices_listed", "mbik_skin_vertices_listed_cpu", "mbik_selftest_math",
+    "mbik_cull_boxes", "mbik_cull_boxes_cpu", "mbik_cull_lod", "mbik_cull_lod_cpu", "mbik_skin_vertices_listed", "mbik_skin_vertices_listed_cpu", "mbik_selftest_math",
     "mbik_selftest_libm", "mbik_selftest_div", "mbik_selftest_qcp", "mbik_selftest_point_in_limits", "mbik_selftest_xform", "mbik_selftest_topology", "mbik_plan_create_device", "mbik_last_error",
 )
 
@@ -109,6 +109,16 @@ class MbikMeshShapes(C.Structure):
 SHAPE_MODES = {"relative": 0, "normalized": 1}  # MBIK_SHAPE_MODE_*
 CULL_MAX_PLANES = 16  # MBIK_CULL_MAX_PLANES
 SKIN_LIST_COMPACT = 1  # MBIK_SKIN_LIST_COMPACT
+
+
+class MbikLodRange(C.Structure):
+    _fields_ = [("begin", C.c_float), ("end", C.c_float), ("begin_margin", C.c_float), ("end_margin", C.c_float)]
+
+
+# mbik_cull_lod: the most ranges a call takes, its flag, and the level of a skeleton in no list
+LOD_MAX_RANGES = 8
+LOD_EXCLUSIVE = 1
+LOD_NONE = 255
 
 
 class MbikError(RuntimeError):
@@ -290,6 +300,10 @@ def load():
     L.mbik_cull_boxes.restype = C.c_int32
     L.mbik_cull_boxes_cpu.argtypes = [C.c_int32, vp, vp, C.c_float, C.c_int32, vp, vp, vp, vp]
     L.mbik_cull_boxes_cpu.restype = C.c_int32
+    L.mbik_cull_lod.argtypes = [vp, C.c_int32, vp, vp, C.c_float, C.c_int32, vp, vp, C.c_int32, vp, C.c_uint32, vp, vp, vp, vp, vp]
+    L.mbik_cull_lod.restype = C.c_int32
+    L.mbik_cull_lod_cpu.argtypes = [C.c_int32, vp, vp, C.c_float, C.c_int32, vp, vp, C.c_int32, vp, C.c_uint32, vp, vp, vp, vp]
+    L.mbik_cull_lod_cpu.restype = C.c_int32
     L.mbik_skin_vertices_listed.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_uint32, vp, vp, vp]
     L.mbik_skin_vertices_listed.restype = C.c_int32
     L.mbik_skin_vertices_listed_cpu.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.POINTER(MbikMeshShapes), C.c_int32,

@@ -192,7 +192,8 @@ struct mbik_mesh {
 	std::vector<uint8_t> bone_used;  // [B]
 	int32_t used_bones = 0;
 	mbik_host::DevBuf bone_table;    // [used_bones] 32-byte records (bone_table_pack)
-	mbik_host::DevBuf cull_totals;   // mbik_cull_boxes' block counts; grows with the largest count seen
+	mbik_host::DevBuf cull_totals;   // mbik_cull_boxes' block counts (mbik_cull_lod's, a row a range); grows with the largest count seen
+	mbik_host::DevBuf lod_member;    // mbik_cull_lod's member bytes, one a skeleton; grows likewise
 };
 
 namespace mbik_host {

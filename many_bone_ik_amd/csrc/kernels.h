@@ -199,6 +199,13 @@ hipError_t launch_skin_bounds(hipStream_t st, int count, int B, int U, int S, co
 constexpr int cull_blocks(int count) { return (int)(((int64_t)count + 255) / 256); }
 hipError_t launch_cull(hipStream_t st, int count, const float *boxes, const float *skeleton_global, float margin, int plane_count,
 		const float *planes, uint8_t *visible, int32_t *indices, int32_t *visible_count, int32_t *totals);
+// k_cull_lod.hip: mbik_cull_lod (lod.h).  The same shape once per range: planes, camera and ranges are host memory, copied into
+// the kernels' arguments; totals is device scratch of range_count * cull_blocks(count) ints and member of count bytes.  Three
+// launches in stream order: state, level, member bytes and block counts; the scan, a row a block; the placement from the bytes.
+struct LodRange;
+hipError_t launch_cull_lod(hipStream_t st, int count, const float *boxes, const float *skeleton_global, float margin, int plane_count,
+		const float *planes, const float *camera, int range_count, const LodRange *ranges, uint32_t flags, uint8_t *state, uint8_t *level,
+		int32_t *indices, int32_t *list_counts, int32_t *totals, uint8_t *member);
 // k_blend.hip: mbik_pose_blend (blend.h).  One thread per bone of the total_bones = count * B, 256 bones a block, 20 KiB
 // of static LDS; influence_per_skeleton (device, [count]) overrides influence when given; pose_out may be pose_in or pose_mod.
 hipError_t launch_blend(hipStream_t st, int64_t total_bones, int B, int libm, float influence, const float *influence_per_skeleton,

@@ -21,6 +21,11 @@ verdicts and the ascending list of visible skeletons (mbik_cull_boxes), all on t
 List-driven skinning (ABI 15): `Mesh.skin_listed()` skins the skeletons a device list
 names -- `Mesh.cull()`'s indices and visible_count, on the same stream and never read by the host --
 in place or compacted (mbik_skin_vertices_listed); `skin_vertices_listed_cpu()` is the host side.
+
+Distance LOD lists: `Mesh.cull_lod()` writes one such list per visibility range
+(mbik_cull_lod: Godot's visibility_range_begin / _end with their margins as hysteresis, in front of the
+plane test), `cull_lod_cpu()` is the host side, and `MeshLod` holds one mesh per level of detail:
+`select()` makes the lists and `skin()` skins each level's mesh over its own.
 """
 from __future__ import annotations
 
@@ -126,6 +131,22 @@ class Mesh:
         check(self._L.mbik_cull_boxes(self.h, count, C.c_void_p(boxes_ptr or None), C.c_void_p(skeleton_global_ptr or None), margin,
                                       pl.shape[0], _ptr(pl) if pl.shape[0] else None, C.c_void_p(visible_ptr or None),
                                       C.c_void_p(indices_ptr or None), C.c_void_p(visible_count_ptr or None), C.c_void_p(stream or None)))
+
+    def cull_lod(self, boxes_ptr: int, count: int, planes, camera, ranges, state_ptr: int, indices_ptr: int, list_counts_ptr: int,
+                 level_ptr: int = 0, skeleton_global_ptr: int = 0, margin: float = 0.0, flags: int = 0, stream: int = 0) -> None:
+        """mbik_cull_lod: cull()'s plane test behind a distance test against `ranges` (host, LOD_RANGE_DTYPE
+        or [n][4]: begin, end, begin_margin, end_margin; 0 = no limit) from `camera` (host, [3]).  state
+        [count] uint8 is read and written (bit r: in range r; the hysteresis; keep it from frame to
+        frame), level [count] uint8 (the least range seen, or LOD_NONE) is optional, indices [n][count]
+        int32 holds list r in row r and list_counts [n] int32 its length: device pointers; asynchronous
+        on `stream`.  flags: _lib.LOD_EXCLUSIVE lists a skeleton under its level only."""
+        pl = np.ascontiguousarray(planes, np.float32).reshape(-1, 4)
+        cam = np.ascontiguousarray(camera, np.float32).reshape(3)
+        rg = lod_ranges(ranges)
+        check(self._L.mbik_cull_lod(self.h, count, C.c_void_p(boxes_ptr or None), C.c_void_p(skeleton_global_ptr or None), margin,
+                                    pl.shape[0], _ptr(pl) if pl.shape[0] else None, _ptr(cam), rg.shape[0], _ptr(rg) if rg.shape[0] else None,
+                                    flags, C.c_void_p(state_ptr or None), C.c_void_p(level_ptr or None), C.c_void_p(indices_ptr or None),
+                                    C.c_void_p(list_counts_ptr or None), C.c_void_p(stream or None)))
 
     def skin_listed(self, skin_ptr: int, out_positions_ptr: int, count: int, indices_ptr: int, list_count_ptr: int,
                     max_list: int | None = None, compact: bool = False, out_normals_ptr: int = 0, shape_weights_ptr: int = 0,
@@ -268,6 +289,73 @@ def cull_boxes_cpu(boxes, planes, skeleton_global=None, margin: float = 0.0):
                                 _ptr(indices), _ptr(n)))
     assert (indices[n[0]:] == -1).all()
     return visible, indices[:n[0]].copy()
+
+
+LOD_RANGE_DTYPE = np.dtype([("begin", np.float32), ("end", np.float32), ("begin_margin", np.float32), ("end_margin", np.float32)])  # mbik_lod_range
+
+
+def lod_ranges(ranges):
+    """-> a contiguous LOD_RANGE_DTYPE array [n] from one, or from rows of (begin, end, begin_margin, end_margin)."""
+    a = np.asarray(ranges)
+    if a.dtype == LOD_RANGE_DTYPE:
+        return np.ascontiguousarray(a).reshape(-1)
+    return np.ascontiguousarray(np.asarray(ranges, np.float32).reshape(-1, 4)).view(LOD_RANGE_DTYPE).reshape(-1)
+
+
+def cull_lod_cpu(boxes, planes, camera, ranges, state, skeleton_global=None, margin: float = 0.0, flags: int = 0):
+    """mbik_cull_lod_cpu (host only): boxes [count][6] against planes [n][4] and `ranges` seen from
+    `camera`, with the previous `state` [count] uint8 (not modified) ->
+    (state [count] uint8, level [count] uint8, lists: one ascending int32 array per range)."""
+    L = _lib.load()
+    bx = np.ascontiguousarray(boxes, np.float32)
+    pl = np.ascontiguousarray(planes, np.float32).reshape(-1, 4)
+    cam = np.ascontiguousarray(camera, np.float32).reshape(3)
+    rg = lod_ranges(ranges)
+    sg = None if skeleton_global is None else np.ascontiguousarray(skeleton_global, np.float32)
+    count, R = bx.shape[0], rg.shape[0]
+    assert bx.shape == (count, 6) and (sg is None or sg.shape == (count, 12)), bx.shape
+    st = np.array(state, np.uint8).reshape(count)
+    level = np.full((count,), 0xEE, np.uint8)
+    indices = np.full((max(R, 1), count), -1, np.int32)
+    n = np.full((max(R, 1),), -1, np.int32)
+    check(L.mbik_cull_lod_cpu(count, _ptr(bx), _ptr(sg), margin, pl.shape[0], _ptr(pl) if pl.shape[0] else None, _ptr(cam), R,
+                              _ptr(rg) if R else None, flags, _ptr(st), _ptr(level), _ptr(indices), _ptr(n)))
+    assert all((indices[r, n[r]:] == -1).all() for r in range(R))
+    return st, level, [indices[r, :n[r]].copy() for r in range(R)]
+
+
+class MeshLod:
+    """One character at several levels of detail: `meshes[r]` is the mesh of range `ranges[r]`, all on
+    one rig and one device.  select() writes one list per range and skin() skins each mesh over its own
+    list; both are asynchronous on `stream` and the host reads nothing in between.  The meshes stay the
+    caller's (close them there)."""
+
+    def __init__(self, meshes, ranges):
+        self.meshes, self.ranges = list(meshes), lod_ranges(ranges)
+        if not self.meshes or len(self.meshes) != self.ranges.shape[0]:
+            raise ValueError("one mesh per range, at least one")
+        if len({m.bone_count for m in self.meshes}) != 1 or len({m.device for m in self.meshes}) != 1:
+            raise ValueError("the meshes of a LOD set share their bone count and their device")
+
+    def select(self, boxes_ptr: int, count: int, planes, camera, state_ptr: int, indices_ptr: int, list_counts_ptr: int,
+               level_ptr: int = 0, skeleton_global_ptr: int = 0, margin: float = 0.0, exclusive: bool = True, stream: int = 0) -> None:
+        """meshes[0].cull_lod(...) with this set's ranges (the first mesh gives the device and the
+        scratch).  exclusive (the default): a skeleton is in the list of its level only, so that
+        overlapping ranges do not skin it twice."""
+        self.meshes[0].cull_lod(boxes_ptr, count, planes, camera, self.ranges, state_ptr, indices_ptr, list_counts_ptr,
+                                level_ptr=level_ptr, skeleton_global_ptr=skeleton_global_ptr, margin=margin,
+                                flags=_lib.LOD_EXCLUSIVE if exclusive else 0, stream=stream)
+
+    def skin(self, skin_ptr: int, out_positions_ptrs, count: int, indices_ptr: int, list_counts_ptr: int, max_lists=None,
+             compact: bool = False, out_normals_ptrs=None, stream: int = 0) -> None:
+        """skin_listed() once per level: meshes[r] over row r of select()'s indices ([ranges][count] int32)
+        with list_counts[r], into out_positions_ptrs[r] (and out_normals_ptrs[r]).  max_lists[r] is the
+        caller's bound on list r's length (it sizes that launch); `count` where not given."""
+        for r, mesh in enumerate(self.meshes):
+            bound = count if max_lists is None else int(max_lists[r])
+            mesh.skin_listed(skin_ptr, out_positions_ptrs[r], count, indices_ptr + 4 * r * count, list_counts_ptr + 4 * r,
+                             max_list=bound, compact=compact, out_normals_ptr=0 if out_normals_ptrs is None else out_normals_ptrs[r],
+                             stream=stream)
 
 
 def synthetic_mesh(parents, rest_globals, vertex_count: int, influences: int, seed: int):
