@@ -649,7 +649,7 @@ int32_t mbik_mesh_launch_shape(const mbik_mesh *mesh, int32_t count, int32_t *sk
  * infinite weights and non-finite shape data propagate.  mbik_skin_vertices_shaped_cpu is the
  * specification and the device gives the same bits.  Deviations from Godot: the shader reads
  * octahedral-packed normals and compressed vertex formats, here every array is float32; tangents
- * are not covered.
+ * are not covered by this call: mbik_skin_vertices_call below carries them.
  *
  * mbik_mesh_create_shaped is mbik_mesh_create with shapes: the same arguments and checks, plus
  * MBIK_EINVAL for a null `shapes`, a struct_size below sizeof(mbik_mesh_shapes), shape_count < 1,
@@ -891,6 +891,75 @@ int32_t mbik_skin_vertices_listed_cpu(int32_t bone_count, int32_t vertex_count, 
 		const float *normals, const int32_t *bone_indices, const float *weights, const mbik_mesh_shapes *shapes, int32_t count,
 		const int32_t *indices, const int32_t *list_count, int32_t max_list, const float *skin, const float *shape_weights,
 		uint32_t flags, float *out_positions, float *out_normals);
+
+/* The tangent stream, and one struct-based call over the plain, the shaped and the listed form
+ * (additive to ABI 15: MBIK_ABI_VERSION stays 15, look the symbols up by name; every entry point above
+ * keeps its signature, checks, texts and bits).  Godot 4.3's skeleton compute shader carries
+ * ARRAY_TANGENT through the same two steps as the normal, the blend-shape pass and the bone
+ * transform; so does this call.  A mesh described by mbik_mesh_desc may have tangents [V][4]: xyz and
+ * the binormal sign w.  mbik_skin_vertices_call_cpu is the specification and the device gives the same
+ * bits.
+ *
+ * With out_tangents == NULL the call IS the existing entry of the same form -- mbik_skin_vertices when
+ * indices, list_count and shape_weights are NULL, mbik_skin_vertices_shaped when only shape_weights is
+ * given, mbik_skin_vertices_listed when the list is given: the same bits, the same refusals with the
+ * same texts, the same kernels.  With out_tangents, for vertex v of the skeleton written to row `row`,
+ * m the blended matrix the position and the normal use, t = tangents[v], float32, unfused, in this
+ * order:
+ *   shaped call only (shape_weights given):
+ *     bt = (0,0,0); inside the ascending loop over the active shapes  bt = bt + shape_tangents[j][v] * c_j
+ *     mode normalized: t.xyz = t.xyz * base_w
+ *     t.xyz = normalized(t.xyz + bt)                 as the normal's: the zero vector stays zero
+ *   every form:
+ *     out_tangents[row][v].xyz = m.basis * t.xyz     the normal's transform, not renormalised
+ *     out_tangents[row][v].w   = the bits of tangents[v][3], copied and never computed with
+ * A plain or listed call without shape_weights on a shaped mesh uses the base tangents without
+ * renormalisation, as the normals.  Deviations from Godot, as before: no octahedral packing, float32
+ * arrays, and the tangent is not re-orthogonalised against the skinned normal.
+ *
+ * mbik_mesh_create_desc is mbik_mesh_create (shapes NULL) or mbik_mesh_create_shaped with the same
+ * checks, and MBIK_EINVAL for a null desc, a struct_size below sizeof(mbik_mesh_desc), tangents
+ * without normals, and shape_tangents on exactly one side of (shapes and tangents both given).  On the
+ * device the tangents lie behind every other plane of the mesh: a mesh without them is the image it
+ * always was.
+ *
+ * mbik_skin_vertices_call: device buffers on the mesh's device, asynchronous on hip_stream.
+ * MBIK_EINVAL: a null call, a struct_size below sizeof(mbik_skin_call), a null mesh, exactly one of
+ * indices and list_count given, out_tangents on a mesh without tangents, out_tangents without
+ * out_normals, out_tangents (rows x vertices x 16 bytes) overlapping skin, shape_weights, indices,
+ * list_count or another output, and everything the matching existing entry refuses.  rows is count,
+ * or max_list for a compact list.  count == 0, max_list == 0 in the listed form or a mesh without
+ * vertices returns MBIK_OK without a launch.  Buffers need float alignment only; element offsets
+ * are 64-bit ((row * vertices + v) * 4 passes 2^31 sooner than the other outputs' x 3).  The _cpu
+ * form takes the mesh as its descriptor (any bone and shape count) with the same checks and texts;
+ * every buffer is host memory. */
+typedef struct mbik_mesh_desc {
+	int32_t struct_size;               /* sizeof(mbik_mesh_desc) */
+	int32_t bone_count, vertex_count, influences;
+	const float *positions;            /* [V][3] */
+	const float *normals;              /* [V][3] or NULL */
+	const float *tangents;             /* [V][4] xyz + binormal sign w, or NULL; needs normals */
+	const int32_t *bone_indices;       /* [V][K] */
+	const float *weights;              /* [V][K] */
+	const mbik_mesh_shapes *shapes;    /* or NULL */
+	const float *shape_tangents;       /* [P][V][3]; given exactly when shapes and tangents both are */
+} mbik_mesh_desc;
+int32_t mbik_mesh_create_desc(const mbik_mesh_desc *desc, int32_t device, mbik_mesh **out_mesh);
+
+typedef struct mbik_skin_call {
+	int32_t struct_size;               /* sizeof(mbik_skin_call) */
+	int32_t count;
+	const float *skin;                 /* [count][bones][12] */
+	const float *shape_weights;        /* [count][P] or NULL */
+	const int32_t *indices;            /* both NULL: the range call over rows 0 .. count-1 */
+	const int32_t *list_count;
+	int32_t max_list;                  /* as mbik_skin_vertices_listed; ignored for the range call */
+	uint32_t flags;
+	float *out_positions, *out_normals; /* [rows][V][3] */
+	float *out_tangents;               /* [rows][V][4] or NULL; needs out_normals */
+} mbik_skin_call;
+int32_t mbik_skin_vertices_call(mbik_mesh *mesh, const mbik_skin_call *call, void *hip_stream);
+int32_t mbik_skin_vertices_call_cpu(const mbik_mesh_desc *desc, const mbik_skin_call *call);
 
 /* Heterogeneous batches: several plans (distinct rigs, e.g. a crowd of different characters)
  * solved by ONE launch, each plan with its own layout.  The reference runs one

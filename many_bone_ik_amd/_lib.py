@@ -38,7 +38,8 @@ EXPORTED_SYMBOLS = (
     "mbik_multi_skeletons", "mbik_multi_destroy", "mbik_capture_targets", "mbik_pose_globals", "mbik_pose_globals_cpu", "mbik_pose_blend", "mbik_pose_blend_cpu", "mbik_clipset_create", "mbik_clipset_destroy", "mbik_clip_sample", "mbik_clip_sample_cpu", "mbik_clip_sample_layers", "mbik_clip_sample_layers_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
     "mbik_skin_vertices", "mbik_skin_vertices_cpu", "mbik_mesh_launch_shape", "mbik_mesh_create_shaped", "mbik_skin_vertices_shaped",
     "mbik_skin_vertices_shaped_cpu", "mbik_mesh_bone_boxes", "mbik_bone_boxes_cpu", "mbik_skin_bounds", "mbik_skin_bounds_cpu",
-    "mbik_cull_boxes", "mbik_cull_boxes_cpu", "mbik_cull_lod", "mbik_cull_lod_cpu", "mbik_skin_vertices_listed", "mbik_skin_vertices_listed_cpu", "mbik_selftest_math",
+    "mbik_cull_boxes", "mbik_cull_boxes_cpu", "mbik_cull_lod", "mbik_cull_lod_cpu", "mbik_skin_vertices_listed", "mbik_skin_vertices_listed_cpu",
+    "mbik_mesh_create_desc", "mbik_skin_vertices_call", "mbik_skin_vertices_call_cpu", "mbik_selftest_math",
     "mbik_selftest_libm", "mbik_selftest_div", "mbik_selftest_qcp", "mbik_selftest_point_in_limits", "mbik_selftest_xform", "mbik_selftest_topology", "mbik_plan_create_device", "mbik_last_error",
 )
 
@@ -106,6 +107,19 @@ class MbikMeshShapes(C.Structure):
                 ("normals", C.c_void_p)]
 
 
+class MbikMeshDesc(C.Structure):  # mbik_mesh_desc
+    _fields_ = [("struct_size", C.c_int32), ("bone_count", C.c_int32), ("vertex_count", C.c_int32), ("influences", C.c_int32),
+                ("positions", C.c_void_p), ("normals", C.c_void_p), ("tangents", C.c_void_p), ("bone_indices", C.c_void_p),
+                ("weights", C.c_void_p), ("shapes", C.POINTER(MbikMeshShapes)), ("shape_tangents", C.c_void_p)]
+
+
+class MbikSkinCall(C.Structure):  # mbik_skin_call
+    _fields_ = [("struct_size", C.c_int32), ("count", C.c_int32), ("skin", C.c_void_p), ("shape_weights", C.c_void_p),
+                ("indices", C.c_void_p), ("list_count", C.c_void_p), ("max_list", C.c_int32), ("flags", C.c_uint32),
+                ("out_positions", C.c_void_p), ("out_normals", C.c_void_p), ("out_tangents", C.c_void_p)]
+
+
+MESH_DESC, SKIN_CALL = MbikMeshDesc, MbikSkinCall
 SHAPE_MODES = {"relative": 0, "normalized": 1}  # MBIK_SHAPE_MODE_*
 CULL_MAX_PLANES = 16  # MBIK_CULL_MAX_PLANES
 SKIN_LIST_COMPACT = 1  # MBIK_SKIN_LIST_COMPACT
@@ -309,6 +323,12 @@ def load():
     L.mbik_skin_vertices_listed_cpu.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.POINTER(MbikMeshShapes), C.c_int32,
                                                 vp, vp, C.c_int32, vp, vp, C.c_uint32, vp, vp]
     L.mbik_skin_vertices_listed_cpu.restype = C.c_int32
+    L.mbik_mesh_create_desc.argtypes = [C.POINTER(MbikMeshDesc), C.c_int32, C.POINTER(vp)]
+    L.mbik_mesh_create_desc.restype = C.c_int32
+    L.mbik_skin_vertices_call.argtypes = [vp, C.POINTER(MbikSkinCall), vp]
+    L.mbik_skin_vertices_call.restype = C.c_int32
+    L.mbik_skin_vertices_call_cpu.argtypes = [C.POINTER(MbikMeshDesc), C.POINTER(MbikSkinCall)]
+    L.mbik_skin_vertices_call_cpu.restype = C.c_int32
     L.mbik_last_error.argtypes = []
     L.mbik_last_error.restype = C.c_char_p
     _lib = L

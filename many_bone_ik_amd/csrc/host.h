@@ -185,8 +185,9 @@ struct mbik_mesh {
 	int device = 0, cu_count = 256;
 	int32_t B = 0, V = 0, K = 4;
 	bool normals = false;
+	bool tangents = false;           // (mbik_mesh_create_desc)
 	int32_t P = 0, mode = 0;         // shapes (P == 0: a mesh without)
-	mbik_host::DevBuf mesh;          // skin_layout()'s planes, then morph_layout()'s
+	mbik_host::DevBuf mesh;          // skin_layout()'s planes, then morph_layout()'s, then tangent_layout()'s
 	// the bone boxes (bounds.h): host copies for mbik_mesh_bone_boxes, and the used bones' records on the device
 	std::vector<float> bone_boxes;   // [B][6]
 	std::vector<uint8_t> bone_used;  // [B]

@@ -6,7 +6,8 @@
 // mbik_mesh_create_shaped, mbik_skin_vertices_shaped and mbik_skin_vertices_shaped_cpu.  The mesh
 // also carries its bone boxes (ABI 14, bounds.h); host_bounds.cpp uses them.
 // List-driven skinning (ABI 15, skin_list.h): mbik_skin_vertices_listed, which launches
-// k_skin_list.hip's kernels, and mbik_skin_vertices_listed_cpu.
+// k_skin_list.hip's kernels, and mbik_skin_vertices_listed_cpu.  The tangent stream and the struct-based call over
+// the three forms: mbik_mesh_create_desc, mbik_skin_vertices_call and mbik_skin_vertices_call_cpu.
 #include "host.h"
 
 #include "bounds.h"
@@ -141,16 +142,26 @@ int launch_on_mesh(const mbik_mesh *m, void *hip_stream, int64_t tiled, mbik::Sk
 	a.st = reinterpret_cast<hipStream_t>(hip_stream);
 	a.K = m->K, a.mode = m->mode, a.B = m->B, a.V = m->V, a.P = m->P;
 	a.S = sh.S, a.chunk = sh.chunk, a.chunks = sh.chunks, a.vshift = sh.vshift;
-	a.mesh = m->mesh.as<unsigned char>(), a.mesh_normals = m->normals;
+	a.mesh = m->mesh.as<unsigned char>(), a.mesh_normals = m->normals, a.mesh_tangents = m->tangents;
 	const hipError_t e = launch(a);
 	if (e != hipSuccess) return fail(MBIK_EHIP, std::string(failed) + hipGetErrorString(e));
 	return MBIK_OK;
 }
 
-// mbik_mesh_create (shaped == false: `shapes` is not looked at) and mbik_mesh_create_shaped
+// The tangent checks mbik_mesh_create_desc and mbik_skin_vertices_call_cpu share.
+int check_tangents(const float *normals, const float *tangents, bool shaped, const float *shape_tangents) {
+	const mbik::SkinCheck c = mbik::skin_check_tangents(normals, tangents);
+	if (c != mbik::SKIN_OK) return fail(MBIK_EINVAL, mbik::skin_check_text(c));
+	const mbik::TangentCheck t = mbik::tangent_check_shapes(shaped, tangents != nullptr, shape_tangents);
+	if (t != mbik::TANGENT_OK) return fail(MBIK_EINVAL, mbik::tangent_check_text(t));
+	return MBIK_OK;
+}
+
+// mbik_mesh_create (shaped == false: `shapes` is not looked at), mbik_mesh_create_shaped and, with tangents [V][4] (and
+// shape_tangents [P][V][3] on a shaped mesh), mbik_mesh_create_desc.  Without tangents the device image is what it always was.
 int create_mesh(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions, const float *normals,
 		const int32_t *bone_indices, const float *weights, bool shaped, const mbik_mesh_shapes *shapes, int32_t device,
-		mbik_mesh **out_mesh) {
+		mbik_mesh **out_mesh, const float *tangents = nullptr, const float *shape_tangents = nullptr) {
 	if (!out_mesh) return fail(MBIK_EINVAL, "null out_mesh");
 	*out_mesh = nullptr;
 	if (influences != 4 && influences != 8) return fail(MBIK_EINVAL, mbik::skin_check_text(mbik::SKIN_BAD_INFLUENCES));
@@ -161,19 +172,23 @@ int create_mesh(int32_t bone_count, int32_t vertex_count, int32_t influences, co
 				std::to_string(mbik::kSkinMaxBones) + " (MBIK_SKIN_MAX_BONES: one skeleton's matrices must fit 160 KiB of LDS)");
 	if (shaped)
 		if (int rc = check_shapes(bone_count, vertex_count, normals != nullptr, shapes, mbik::kSkinMaxLdsBytes)) return rc;
+	if (int rc = check_tangents(normals, tangents, shaped, shape_tangents)) return rc;
 	if (int rc = check_mesh(bone_count, vertex_count, influences, positions, bone_indices, weights)) return rc;
 	if (int rc = check_device(device)) return rc;
 	std::unique_ptr<mbik_mesh> m(new mbik_mesh());
 	m->device = device, m->B = bone_count, m->V = vertex_count, m->K = influences, m->normals = normals != nullptr;
+	m->tangents = tangents != nullptr;
 	if (shaped) m->P = shapes->shape_count, m->mode = shapes->mode;
 	DeviceGuard guard(device);
 	m->cu_count = cu_count_of(device);
 	if (vertex_count > 0) {
 		const mbik::SkinLayout l = mbik::skin_layout(vertex_count, influences, m->normals);
-		const int64_t bytes = shaped ? mbik::morph_layout(vertex_count, influences, m->normals, m->P).bytes : l.bytes;
+		int64_t bytes = shaped ? mbik::morph_layout(vertex_count, influences, m->normals, m->P).bytes : l.bytes;
+		if (tangents) bytes = mbik::tangent_layout(vertex_count, influences, true, m->P, true).bytes;
 		std::vector<unsigned char> packed((size_t)bytes);
 		mbik::skin_pack(vertex_count, influences, positions, normals, bone_indices, weights, packed.data());
 		if (shaped) mbik::morph_pack(vertex_count, influences, m->P, shapes->positions, shapes->normals, packed.data());
+		if (tangents) mbik::tangent_pack(vertex_count, influences, m->P, tangents, shape_tangents, packed.data());
 		if (int rc = m->mesh.reserve(packed.size(), "hipMalloc failed for the mesh")) return rc;
 		if (hipMemcpy(m->mesh.as<void>(), packed.data(), packed.size(), hipMemcpyHostToDevice) != hipSuccess)
 			return fail(MBIK_EHIP, "hipMemcpy failed for the mesh");
@@ -193,9 +208,106 @@ int create_mesh(int32_t bone_count, int32_t vertex_count, int32_t influences, co
 	return MBIK_OK;
 }
 
+// ---- mbik_skin_vertices_call and its _cpu form ----
+struct MeshFacts {
+	int32_t B, V, P;
+	bool normals, tangents;
+};
+
+int check_call_struct(const mbik_skin_call *c) {
+	if (!c) return fail(MBIK_EINVAL, "null call");
+	if (c->struct_size < (int32_t)sizeof(mbik_skin_call)) return fail(MBIK_EINVAL, "mbik_skin_call.struct_size is too small");
+	return MBIK_OK;
+}
+
+// The checks both entries run on a call past its struct's own: the form's existing checks with their texts, then the
+// tangent output's.  0 = run, 1 = nothing to do.
+int check_skin_call(const MeshFacts &f, const mbik_skin_call *c) {
+	if ((c->indices != nullptr) != (c->list_count != nullptr)) return fail(MBIK_EINVAL, "indices and list_count must be given together");
+	if (c->out_tangents && !f.tangents) return fail(MBIK_EINVAL, "out_tangents given for a mesh without tangents");
+	if (c->out_tangents && !c->out_normals) return fail(MBIK_EINVAL, "out_tangents given without out_normals");
+	const bool listed = c->indices != nullptr;
+	int64_t rows = c->count;
+	if (listed) {
+		if (int rc = check_listed(f.B, f.V, f.normals, f.P, c->count, c->indices, c->list_count, c->max_list, c->skin, c->shape_weights,
+					c->flags, c->out_positions, c->out_normals))
+			return rc;
+		rows = (c->flags & mbik::kSkinListCompact) ? c->max_list : c->count;
+	} else {
+		if (c->shape_weights && f.P < 1) return fail(MBIK_EINVAL, "the mesh has no shapes (mbik_mesh_create_shaped)");
+		if (int rc = check_call(f.B, f.V, f.normals, c->count, c->skin, c->out_positions, c->out_normals)) return rc;
+		if (c->shape_weights)
+			if (int rw = check_shape_weights(f.V, f.P, c->count, c->shape_weights, c->out_positions, c->out_normals)) return rw;
+	}
+	if (!c->out_tangents) return 0;
+	const size_t nt = (size_t)rows * f.V * 4 * sizeof(float), nout = (size_t)rows * f.V * 3 * sizeof(float);
+	const auto hit = [&](const void *p, size_t n) { return p && overlap(p, n, c->out_tangents, nt); };
+	if (hit(c->skin, (size_t)c->count * f.B * 12 * sizeof(float))) return fail(MBIK_EINVAL, "out_tangents overlaps skin");
+	if (hit(c->shape_weights, (size_t)c->count * f.P * sizeof(float))) return fail(MBIK_EINVAL, "out_tangents overlaps shape_weights");
+	if (listed && hit(c->indices, (size_t)c->max_list * sizeof(int32_t))) return fail(MBIK_EINVAL, "out_tangents overlaps indices");
+	if (listed && hit(c->list_count, sizeof(int32_t))) return fail(MBIK_EINVAL, "out_tangents overlaps list_count");
+	if (hit(c->out_positions, nout)) return fail(MBIK_EINVAL, "out_tangents overlaps out_positions");
+	if (hit(c->out_normals, nout)) return fail(MBIK_EINVAL, "out_tangents overlaps out_normals");
+	return 0;
+}
+
+int check_desc_struct(const mbik_mesh_desc *d) {
+	if (!d) return fail(MBIK_EINVAL, "null desc");
+	if (d->struct_size < (int32_t)sizeof(mbik_mesh_desc)) return fail(MBIK_EINVAL, "mbik_mesh_desc.struct_size is too small");
+	return MBIK_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int32_t mbik_mesh_create_desc(const mbik_mesh_desc *d, int32_t device, mbik_mesh **out_mesh) {
+	if (out_mesh) *out_mesh = nullptr;
+	if (int rc = check_desc_struct(d)) return rc;
+	return create_mesh(d->bone_count, d->vertex_count, d->influences, d->positions, d->normals, d->bone_indices, d->weights,
+			d->shapes != nullptr, d->shapes, device, out_mesh, d->tangents, d->shape_tangents);
+}
+
+int32_t mbik_skin_vertices_call(mbik_mesh *m, const mbik_skin_call *c, void *hip_stream) {
+	if (int rc = check_call_struct(c)) return rc;
+	if (!m) return fail(MBIK_EINVAL, "null mesh");
+	const int rc = check_skin_call(MeshFacts{m->B, m->V, m->P, m->normals, m->tangents}, c);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	mbik::SkinLaunch a{};
+	a.count = c->count, a.skin = c->skin, a.shape_weights = c->shape_weights;
+	a.out_p = c->out_positions, a.out_n = c->out_normals, a.out_t = c->out_tangents;
+	if (!c->indices)
+		return launch_on_mesh(m, hip_stream, c->count, a, mbik::launch_skin,
+				c->shape_weights ? "shaped skinning launch failed: " : "skinning launch failed: ");
+	a.indices = c->indices, a.list_count = c->list_count, a.max_list = c->max_list, a.compact = (c->flags & mbik::kSkinListCompact) != 0;
+	return launch_on_mesh(m, hip_stream, c->max_list, a, mbik::launch_skin_listed, "listed skinning launch failed: ");
+}
+
+int32_t mbik_skin_vertices_call_cpu(const mbik_mesh_desc *d, const mbik_skin_call *c) {
+	if (int rc = check_desc_struct(d)) return rc;
+	if (int rc = check_call_struct(c)) return rc;
+	if (int rc = check_mesh(d->bone_count, d->vertex_count, d->influences, d->positions, d->bone_indices, d->weights)) return rc;
+	if (d->shapes)
+		if (int rc = check_shapes(d->bone_count, d->vertex_count, d->normals != nullptr, d->shapes, -1)) return rc;
+	if (int rc = check_tangents(d->normals, d->tangents, d->shapes != nullptr, d->shape_tangents)) return rc;
+	const int32_t P = d->shapes ? d->shapes->shape_count : 0;
+	const int rc = check_skin_call(MeshFacts{d->bone_count, d->vertex_count, P, d->normals != nullptr, d->tangents != nullptr}, c);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	const float *tan = c->out_tangents ? d->tangents : nullptr, *stan = c->out_tangents ? d->shape_tangents : nullptr;
+	if (c->indices)
+		mbik::skin_vertices_listed_host(d->bone_count, d->vertex_count, d->influences, d->positions, d->normals, d->bone_indices, d->weights,
+				P, d->shapes ? d->shapes->mode : 0, d->shapes ? d->shapes->positions : nullptr, d->shapes ? d->shapes->normals : nullptr,
+				c->count, c->indices, c->list_count, c->max_list, c->skin, c->shape_weights, (c->flags & mbik::kSkinListCompact) != 0,
+				c->out_positions, c->out_normals, tan, stan, c->out_tangents);
+	else if (c->shape_weights)
+		mbik::morph_skin_vertices_host(d->bone_count, d->vertex_count, d->influences, d->positions, d->normals, d->bone_indices, d->weights,
+				P, d->shapes->mode, d->shapes->positions, d->shapes->normals, c->count, c->skin, c->shape_weights, c->out_positions,
+				c->out_normals, tan, stan, c->out_tangents);
+	else
+		mbik::skin_vertices_host(d->bone_count, d->vertex_count, d->influences, d->positions, d->normals, d->bone_indices, d->weights,
+				c->count, c->skin, c->out_positions, c->out_normals, tan, c->out_tangents);
+	return MBIK_OK;
+}
 
 int32_t mbik_mesh_create(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions, const float *normals,
 		const int32_t *bone_indices, const float *weights, int32_t device, mbik_mesh **out_mesh) {

@@ -11,7 +11,7 @@
 //
 // A thread loops over the block's skeletons with one vertex in registers: the shape walk, K matrix
 // reads, the blend, the transform, one 12-byte store per output (consecutive lanes are consecutive
-// vertices: 768 contiguous bytes a wave).  Meshes with fewer vertices in a chunk than the block has
+// vertices: 768 contiguous bytes a wave), and in the tangent tier one 16-byte store more.  Meshes with fewer vertices in a chunk than the block has
 // threads give the spare waves other skeletons of the tile.
 #include <mutex>
 
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(kSkinThreads) void mbik_skin_kernel(int count, int 
 		const float4 *__restrict__ m_wgt, int64_t wplane, const float *__restrict__ skin, float *__restrict__ out_p,
 		float *__restrict__ out_n) {
 	extern __shared__ __attribute__((aligned(16))) float skin_lds[];
-	skin_block<K, NRM, kNoShapes>(range_tile(count, S), skin_lds, B, V, 0, S, chunk, vshift, m_pos, m_nrm, m_idx, m_wgt, nullptr, nullptr,
+	skin_block<K, skin_tier(NRM, false), kNoShapes>(range_tile(count, S), skin_lds, B, V, 0, S, chunk, vshift, m_pos, m_nrm, m_idx, m_wgt, nullptr, nullptr,
 			wplane, skin, nullptr, out_p, out_n);
 }
 
@@ -61,15 +61,44 @@ __global__ __launch_bounds__(kSkinThreads) void mbik_skin_shaped_kernel(int coun
 		const float *__restrict__ skin, const float *__restrict__ shape_weights, float *__restrict__ out_p,
 		float *__restrict__ out_n) {
 	extern __shared__ __attribute__((aligned(16))) float skin_lds[];
-	skin_block<K, NRM, MODE>(range_tile(count, S), skin_lds, B, V, P, S, chunk, vshift, m_pos, m_nrm, m_idx, m_wgt, m_spos, m_snrm, wplane,
+	skin_block<K, skin_tier(NRM, false), MODE>(range_tile(count, S), skin_lds, B, V, P, S, chunk, vshift, m_pos, m_nrm, m_idx, m_wgt, m_spos, m_snrm, wplane,
 			skin, shape_weights, out_p, out_n);
 }
 
+// The tangent tier (mbik_skin_vertices_call with out_tangents): the same two argument lists with
+// the tangent planes behind the normals' and the third output last.
+template <int K>
+__global__ __launch_bounds__(kSkinThreads) void mbik_skin_tan_kernel(int count, int B, int V, int S, int chunk, int vshift,
+		const float4 *__restrict__ m_pos, const float4 *__restrict__ m_nrm, const float4 *__restrict__ m_tan,
+		const uint2 *__restrict__ m_idx, const float4 *__restrict__ m_wgt, int64_t wplane, const float *__restrict__ skin,
+		float *__restrict__ out_p, float *__restrict__ out_n, float *__restrict__ out_t) {
+	extern __shared__ __attribute__((aligned(16))) float skin_lds[];
+	skin_block<K, SKIN_TANGENTS, kNoShapes>(range_tile(count, S), skin_lds, B, V, 0, S, chunk, vshift, m_pos, m_nrm, m_idx, m_wgt, nullptr,
+			nullptr, wplane, skin, nullptr, out_p, out_n, SkinTangents{m_tan, nullptr, out_t});
+}
+
+template <int K, int MODE>
+__global__ __launch_bounds__(kSkinThreads) void mbik_skin_tan_shaped_kernel(int count, int B, int V, int P, int S, int chunk, int vshift,
+		const float4 *__restrict__ m_pos, const float4 *__restrict__ m_nrm, const float4 *__restrict__ m_tan,
+		const uint2 *__restrict__ m_idx, const float4 *__restrict__ m_wgt, const float4 *__restrict__ m_spos,
+		const float4 *__restrict__ m_snrm, const float4 *__restrict__ m_stan, int64_t wplane, const float *__restrict__ skin,
+		const float *__restrict__ shape_weights, float *__restrict__ out_p, float *__restrict__ out_n, float *__restrict__ out_t) {
+	extern __shared__ __attribute__((aligned(16))) float skin_lds[];
+	skin_block<K, SKIN_TANGENTS, MODE>(range_tile(count, S), skin_lds, B, V, P, S, chunk, vshift, m_pos, m_nrm, m_idx, m_wgt, m_spos, m_snrm,
+			wplane, skin, shape_weights, out_p, out_n, SkinTangents{m_tan, m_stan, out_t});
+}
+
 struct RangeKernels {
-	template <int K, bool NRM, int MODE>
+	template <int K, int TIER, int MODE>
 	static auto kernel() {
-		if constexpr (MODE == kNoShapes) return &mbik_skin_kernel<K, NRM>;
-		else return &mbik_skin_shaped_kernel<K, NRM, MODE>;
+		if constexpr (TIER == SKIN_TANGENTS) {
+			if constexpr (MODE == kNoShapes) return &mbik_skin_tan_kernel<K>;
+			else return &mbik_skin_tan_shaped_kernel<K, MODE>;
+		} else {
+			constexpr bool NRM = TIER == SKIN_NORMALS;
+			if constexpr (MODE == kNoShapes) return &mbik_skin_kernel<K, NRM>;
+			else return &mbik_skin_shaped_kernel<K, NRM, MODE>;
+		}
 	}
 };
 } // namespace

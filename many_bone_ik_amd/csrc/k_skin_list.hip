@@ -84,7 +84,7 @@ void mbik_skin_list_kernel(int count, int B, int V, int S, int chunk, int vshift
 		const float4 *__restrict__ m_wgt, int64_t wplane, const float *__restrict__ skin, const int32_t *__restrict__ indices,
 		const int32_t *__restrict__ list_count, int max_list, int compact, float *__restrict__ out_p, float *__restrict__ out_n) {
 	extern __shared__ __attribute__((aligned(16))) float skin_lds[];
-	skin_block<K, NRM, kNoShapes>(list_tile(count, S, indices, list_count, max_list, compact), skin_lds, B, V, 0, S, chunk, vshift, m_pos,
+	skin_block<K, skin_tier(NRM, false), kNoShapes>(list_tile(count, S, indices, list_count, max_list, compact), skin_lds, B, V, 0, S, chunk, vshift, m_pos,
 			m_nrm, m_idx, m_wgt, nullptr, nullptr, wplane, skin, nullptr, out_p, out_n);
 }
 
@@ -96,15 +96,52 @@ void mbik_skin_list_shaped_kernel(int count, int B, int V, int P, int S, int chu
 		const float *__restrict__ skin, const float *__restrict__ shape_weights, const int32_t *__restrict__ indices,
 		const int32_t *__restrict__ list_count, int max_list, int compact, float *__restrict__ out_p, float *__restrict__ out_n) {
 	extern __shared__ __attribute__((aligned(16))) float skin_lds[];
-	skin_block<K, NRM, MODE>(list_tile(count, S, indices, list_count, max_list, compact), skin_lds, B, V, P, S, chunk, vshift, m_pos, m_nrm,
+	skin_block<K, skin_tier(NRM, false), MODE>(list_tile(count, S, indices, list_count, max_list, compact), skin_lds, B, V, P, S, chunk, vshift, m_pos, m_nrm,
 			m_idx, m_wgt, m_spos, m_snrm, wplane, skin, shape_weights, out_p, out_n);
 }
 
+// The tangent tier: k_skin.hip's two tangent argument lists with the list's in front of the outputs.
+// The plain kernels' targets are one wave under the normals tier's: the tangent and its sign are four registers more.  The
+// shaped ones are compiled for 4 waves: with 5 the relative K = 4 kernel came out at 96 VGPRs and one spilled register, with 4
+// it takes 97 and none; the normalized K = 4 one stays at 83, which runs 5 waves all the same.
+constexpr int list_tan_waves(int K, bool shaped) { return shaped ? 4 : list_waves(K, true, shaped) - 1; }
+
+template <int K>
+__global__ __launch_bounds__(kSkinThreads) __attribute__((amdgpu_waves_per_eu(list_tan_waves(K, false))))
+void mbik_skin_list_tan_kernel(int count, int B, int V, int S, int chunk, int vshift,
+		const float4 *__restrict__ m_pos, const float4 *__restrict__ m_nrm, const float4 *__restrict__ m_tan,
+		const uint2 *__restrict__ m_idx, const float4 *__restrict__ m_wgt, int64_t wplane, const float *__restrict__ skin,
+		const int32_t *__restrict__ indices, const int32_t *__restrict__ list_count, int max_list, int compact,
+		float *__restrict__ out_p, float *__restrict__ out_n, float *__restrict__ out_t) {
+	extern __shared__ __attribute__((aligned(16))) float skin_lds[];
+	skin_block<K, SKIN_TANGENTS, kNoShapes>(list_tile(count, S, indices, list_count, max_list, compact), skin_lds, B, V, 0, S, chunk, vshift,
+			m_pos, m_nrm, m_idx, m_wgt, nullptr, nullptr, wplane, skin, nullptr, out_p, out_n, SkinTangents{m_tan, nullptr, out_t});
+}
+
+template <int K, int MODE>
+__global__ __launch_bounds__(kSkinThreads) __attribute__((amdgpu_waves_per_eu(list_tan_waves(K, true))))
+void mbik_skin_list_tan_shaped_kernel(int count, int B, int V, int P, int S, int chunk, int vshift,
+		const float4 *__restrict__ m_pos, const float4 *__restrict__ m_nrm, const float4 *__restrict__ m_tan,
+		const uint2 *__restrict__ m_idx, const float4 *__restrict__ m_wgt, const float4 *__restrict__ m_spos,
+		const float4 *__restrict__ m_snrm, const float4 *__restrict__ m_stan, int64_t wplane, const float *__restrict__ skin,
+		const float *__restrict__ shape_weights, const int32_t *__restrict__ indices, const int32_t *__restrict__ list_count,
+		int max_list, int compact, float *__restrict__ out_p, float *__restrict__ out_n, float *__restrict__ out_t) {
+	extern __shared__ __attribute__((aligned(16))) float skin_lds[];
+	skin_block<K, SKIN_TANGENTS, MODE>(list_tile(count, S, indices, list_count, max_list, compact), skin_lds, B, V, P, S, chunk, vshift, m_pos,
+			m_nrm, m_idx, m_wgt, m_spos, m_snrm, wplane, skin, shape_weights, out_p, out_n, SkinTangents{m_tan, m_stan, out_t});
+}
+
 struct ListKernels {
-	template <int K, bool NRM, int MODE>
+	template <int K, int TIER, int MODE>
 	static auto kernel() {
-		if constexpr (MODE == kNoShapes) return &mbik_skin_list_kernel<K, NRM>;
-		else return &mbik_skin_list_shaped_kernel<K, NRM, MODE>;
+		if constexpr (TIER == SKIN_TANGENTS) {
+			if constexpr (MODE == kNoShapes) return &mbik_skin_list_tan_kernel<K>;
+			else return &mbik_skin_list_tan_shaped_kernel<K, MODE>;
+		} else {
+			constexpr bool NRM = TIER == SKIN_NORMALS;
+			if constexpr (MODE == kNoShapes) return &mbik_skin_list_kernel<K, NRM>;
+			else return &mbik_skin_list_shaped_kernel<K, NRM, MODE>;
+		}
 	}
 };
 } // namespace

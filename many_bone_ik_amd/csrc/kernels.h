@@ -168,7 +168,7 @@ hipError_t launch_fk(hipStream_t st, int count, int B, int P, int S, int levels,
 // groups that share a tile's S slots.  mesh is the device copy in skin_layout()'s planes, with morph_layout()'s shape planes
 // behind them when the mesh has shapes; out_n null = positions only.  shape_weights (device, [count][P]) null = no shapes:
 // S * B * 48 bytes of LDS a block, otherwise S * (B * 48 + P * 4), the tile's shape weights behind its matrices; mode is
-// the mesh's MorphMode.
+// the mesh's MorphMode.  Tangents add no per-skeleton data, so the LDS and the launch shape do not know of them.
 struct SkinLaunch {
 	hipStream_t st;
 	int K, mode, count, B, V, P, S, chunk, chunks, vshift;
@@ -176,6 +176,10 @@ struct SkinLaunch {
 	bool mesh_normals;
 	const float *skin, *shape_weights;
 	float *out_p, *out_n;
+	// the tangent tier (mbik_skin_vertices_call): out_t [rows][V][4] with out_n, on a mesh with tangents, whose planes
+	// (tangent_layout()) lie behind the shape planes; null = the kernels of the other two tiers
+	float *out_t;
+	bool mesh_tangents;
 	// launch_skin_listed only: indices (device, [max_list]) and list_count (device, [1]) are read by the kernel only, which
 	// tests every entry against [0, count); compact: entry r writes output row r, otherwise row indices[r]
 	const int32_t *indices, *list_count;

@@ -9,6 +9,9 @@
 //     M    = M + X_k * w_k   k = 1..K-1    in influence order; every influence, weight 0 included
 //     pos' = xform(M, pos)                 ((r.x*v.x + r.y*v.y) + r.z*v.z) + o per row
 //     nrm' = xform(M.b, nrm)               same matrix, no origin, not renormalised
+//     tan' = xform(M.b, tan.xyz), tan.w    the normal's transform on ARRAY_TANGENT's xyz; the binormal
+//                                          sign w is copied, its bits untouched (mbik_skin_vertices_call,
+//                                          DESIGN.md §22)
 //
 // One code path for both sides, built only from gd_math.h's primitives and compiled with
 // -ffp-contract=off, so the device and the host produce the same bits.  Weights are used as
@@ -57,8 +60,12 @@ GDI X3 skin_accumulate(const X3 &m, const X3 &x, float w) {
 GDI V3 skin_position(const X3 &m, V3 pos) { return xform(m, pos); }
 GDI V3 skin_normal(const X3 &m, V3 nrm) { return xform(m.b, nrm); }
 
+// What a call writes for a vertex: the attribute tier of the kernels and of the host path.
+enum SkinTier { SKIN_POSITIONS = 0, SKIN_NORMALS = 1, SKIN_TANGENTS = 2 };
+constexpr int skin_tier(bool normals, bool tangents) { return tangents ? SKIN_TANGENTS : (normals ? SKIN_NORMALS : SKIN_POSITIONS); }
+
 // ---------------- validation (the checks mbik_mesh_create and mbik_skin_vertices_cpu share) ----------------
-enum SkinCheck { SKIN_OK = 0, SKIN_BAD_INFLUENCES, SKIN_NEGATIVE, SKIN_NULL, SKIN_BAD_INDEX };
+enum SkinCheck { SKIN_OK = 0, SKIN_BAD_INFLUENCES, SKIN_NEGATIVE, SKIN_NULL, SKIN_BAD_INDEX, SKIN_TANGENTS_WITHOUT_NORMALS };
 // bad_vertex / bad_slot: where the first index outside [0, B) is (SKIN_BAD_INDEX)
 inline SkinCheck skin_check_mesh(int32_t B, int32_t V, int32_t K, const float *positions, const int32_t *bone_indices,
 		const float *weights, int64_t *bad_vertex = nullptr, int *bad_slot = nullptr) {
@@ -76,12 +83,17 @@ inline SkinCheck skin_check_mesh(int32_t B, int32_t V, int32_t K, const float *p
 		}
 	return SKIN_OK;
 }
+// a mesh's tangents ([V][4]: xyz and the binormal sign) come with its normals
+inline SkinCheck skin_check_tangents(const float *normals, const float *tangents) {
+	return tangents && !normals ? SKIN_TANGENTS_WITHOUT_NORMALS : SKIN_OK;
+}
 inline const char *skin_check_text(SkinCheck c) {
 	switch (c) {
 		case SKIN_BAD_INFLUENCES: return "influences must be 4 or 8";
 		case SKIN_NEGATIVE: return "negative bone or vertex count";
 		case SKIN_NULL: return "null mesh array";
 		case SKIN_BAD_INDEX: return "bone index outside [0, bone_count)";
+		case SKIN_TANGENTS_WITHOUT_NORMALS: return "tangents given for a mesh without normals";
 		default: return "ok";
 	}
 }
@@ -94,6 +106,8 @@ inline const char *skin_check_text(SkinCheck c) {
 //   indices    [V] 2 B x K  bone indices, 16 bits each in influence order (8 B for K = 4, 16 B for K = 8)
 //   weights    [K / 4][V] 16 B   influences 4q .. 4q + 3 of plane q
 // Every plane starts at a multiple of 16 bytes.  Offsets are in bytes from the mesh's base.
+// A mesh with tangents keeps them in one more plane behind these and behind morph.h's shape planes
+// (tangent_layout there), so that no offset here depends on them.
 struct SkinLayout {
 	int64_t pos, nrm, idx, wgt, bytes; // nrm = -1 for a mesh without normals
 };
@@ -129,9 +143,9 @@ inline void skin_pack(int32_t V, int32_t K, const float *positions, const float 
 
 // ---------------- host path ----------------
 // One vertex of one skeleton: skin = that skeleton's [B][12] matrices, idx / w the vertex's K
-// influences; out_n (and nrm) may be null.
+// influences; out_n (and nrm) may be null; tan [4] and out_t [4] likewise (given with out_n only).
 inline void skin_vertex_host(int K, const float *skin, const int32_t *idx, const float *w, const float *pos, const float *nrm,
-		float *out_p, float *out_n) {
+		float *out_p, float *out_n, const float *tan = nullptr, float *out_t = nullptr) {
 	X3 m = skin_scaled(skin_load(skin + (int64_t)idx[0] * 12), w[0]);
 	for (int k = 1; k < K; k++) m = skin_accumulate(m, skin_load(skin + (int64_t)idx[k] * 12), w[k]);
 	const V3 p = skin_position(m, v3(pos[0], pos[1], pos[2]));
@@ -140,16 +154,23 @@ inline void skin_vertex_host(int K, const float *skin, const int32_t *idx, const
 		const V3 q = skin_normal(m, v3(nrm[0], nrm[1], nrm[2]));
 		out_n[0] = q.x, out_n[1] = q.y, out_n[2] = q.z;
 	}
+	if (out_t) {
+		const V3 t = skin_normal(m, v3(tan[0], tan[1], tan[2]));
+		out_t[0] = t.x, out_t[1] = t.y, out_t[2] = t.z;
+		memcpy(out_t + 3, tan + 3, 4); // (the sign's bits: never a float in a register)
+	}
 }
-// count skeletons of a checked mesh: skin [count][B][12], out_positions / out_normals [count][V][3]
+// count skeletons of a checked mesh: skin [count][B][12], out_positions / out_normals [count][V][3];
+// tangents [V][4] and out_tangents [count][V][4], or null
 inline void skin_vertices_host(int32_t B, int32_t V, int32_t K, const float *positions, const float *normals,
 		const int32_t *bone_indices, const float *weights, int32_t count, const float *skin, float *out_positions,
-		float *out_normals) {
+		float *out_normals, const float *tangents = nullptr, float *out_tangents = nullptr) {
 	for (int64_t s = 0; s < count; s++)
 		for (int64_t v = 0; v < V; v++)
 			skin_vertex_host(K, skin + s * B * 12, bone_indices + v * K, weights + v * K, positions + v * 3,
 					out_normals ? normals + v * 3 : nullptr, out_positions + (s * V + v) * 3,
-					out_normals ? out_normals + (s * V + v) * 3 : nullptr);
+					out_normals ? out_normals + (s * V + v) * 3 : nullptr, out_tangents ? tangents + v * 4 : nullptr,
+					out_tangents ? out_tangents + (s * V + v) * 4 : nullptr);
 }
 
 } // namespace mbik

@@ -1,7 +1,8 @@
 // What the skinning kernel TUs (k_skin.hip, k_skin_list.hip) share, which is everything but what a
 // tile is: the block size, one vertex in registers and its load, the shape step, and the block's body
 // from the early return to the vertex loop with the blend and its 12-byte stores (skin_block); on the
-// host side the K x normals x mode dispatch with the launch built on it.  A TU adds its tile policy
+// host side the K x tier x mode dispatch with the launch built on it.  The tier (skin.h's SkinTier) says
+// what a vertex carries: the position, the normal with it, or the tangent with both.  A TU adds its tile policy
 // and its __global__ entry points, which form the tile, call skin_block and carry the attributes that
 // differ.
 //
@@ -16,8 +17,10 @@
 //                      get to lds + s * n;
 //   link(wlds, P)      the link pass over the staged slots' weights (morph_link_skipped), a slot a
 //                      thread; a slot that was not staged is not linked.
-// Everything here is forced inline, and the 24 kernels keep the registers of the hand-written loops
-// they replace (profiles/skin_refactor_regs.json); the shaped ones keep their instruction counts too.
+// Everything here is forced inline, and the 24 kernels of the first two tiers keep the registers of the
+// hand-written loops they replace (profiles/skin_refactor_regs.json); the shaped ones keep their instruction
+// counts too.  The tangent tier's 12 kernels are `if constexpr` additions to the same body and leave the 24
+// as they were, instruction for instruction (profiles/skin_tangent_regs.json).
 // Four things sit where they do for that (DESIGN.md §19 has the figures): a run's length comes as its
 // two factors (RangeTile multiplies s0 * items * width in the hand-written order; the same loop three
 // instructions further up measured 1.4 % slower at C5), the link pass is the tile's (shared as one
@@ -53,6 +56,25 @@ __device__ __forceinline__ void skin_store3(float *o, V3 p) {
 	o[0] = p.x, o[1] = p.y, o[2] = p.z;
 #endif
 }
+
+// The tangent's 16 bytes a lane: x, y, z and the binormal sign, whose bits are only moved.  Four dword
+// stores in the source, as skin_store3's three: the outputs need float alignment only, and the backend
+// merges them into one global_store_dwordx4, 1,024 contiguous bytes a wave.
+__device__ __forceinline__ void skin_store4(float *o, V3 p, float w) {
+#ifdef MBIK_SKIN_NT
+	__builtin_nontemporal_store(p.x, o), __builtin_nontemporal_store(p.y, o + 1), __builtin_nontemporal_store(p.z, o + 2);
+	__builtin_nontemporal_store(w, o + 3);
+#else
+	o[0] = p.x, o[1] = p.y, o[2] = p.z, o[3] = w;
+#endif
+}
+
+// The tangent tier's planes and output, null in the other tiers: m_tan the base tangents (x, y, z, w a
+// vertex), m_stan the shape tangents of shape 0 (the next shape's wplane records on), out_t [rows][V][4].
+struct SkinTangents {
+	const float4 *__restrict__ m_tan = nullptr, *__restrict__ m_stan = nullptr;
+	float *__restrict__ out_t = nullptr;
+};
 
 // One vertex as a thread keeps it: position, normal (zero without NRM), the bones' quad offsets inside
 // one skeleton's LDS image, and the weights.
@@ -91,29 +113,31 @@ __device__ __forceinline__ SkinVertex<K> skin_load_vertex(const float4 *__restri
 // with its arithmetic; skin_link_weights has turned every skipped weight into the index of the next
 // active shape, so the walk steps from active shape to active shape.  sp / sn: the vertex's record of
 // shape 0, 16 bytes a lane, the next shape's wplane records on.
-template <bool NRM, int MODE>
+// st: the shape tangents likewise (tangent tier), requested with the other two records in front of the one barrier.
+template <int TIER, int MODE>
 __device__ __forceinline__ void skin_shape_vertex(int P, const float *cs, const float4 *__restrict__ sp, const float4 *__restrict__ sn,
-		int64_t wplane, V3 &pos, V3 &nrm) {
-	float4 rn = make_float4(0, 0, 0, 0);
-	morph_vertex<NRM>(
+		const float4 *__restrict__ st, int64_t wplane, V3 &pos, V3 &nrm, V3 &tan) {
+	constexpr bool NRM = TIER >= SKIN_NORMALS, TAN = TIER >= SKIN_TANGENTS;
+	float4 rn = make_float4(0, 0, 0, 0), rt = make_float4(0, 0, 0, 0);
+	morph_vertex_tier<TIER>(
 			MODE, P, [&](int j) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, cs[j]))); },
 #ifndef MBIK_MORPH_SCAN
 			[](int, float c) { return morph_link(c); },
 #else // A/B build: every vertex walks all P weights of its skeleton
 			[](int j, float) { return j + 1; },
 #endif
-			// (both records are requested before the first is waited for: the scheduler otherwise
+			// (every record is requested before the first is waited for: the scheduler otherwise
 			// puts the position's arithmetic, and its wait, in front of the normal's load)
 			[&](int j) {
 				const float4 r = sp[j * wplane];
 				if constexpr (NRM) {
 					rn = sn[j * wplane];
+					if constexpr (TAN) rt = st[j * wplane];
 					__builtin_amdgcn_sched_barrier(0);
 				}
 				return v3(r.x, r.y, r.z);
 			},
-			[&](int) { return v3(rn.x, rn.y, rn.z); },
-			pos, nrm);
+			[&](int) { return v3(rn.x, rn.y, rn.z); }, [&](int) { return v3(rt.x, rt.y, rt.z); }, pos, nrm, tan);
 }
 
 // The staged weights of the tile's slots, P a slot, linked for skin_shape_vertex.  Every thread of the
@@ -131,12 +155,14 @@ __device__ __forceinline__ void skin_link_weights(const Tile &t, float *wlds, in
 // 16-byte quads; with shapes the tile's weights (P a slot) are staged behind the S x B x 12 matrices.
 // The block is `vlanes` vertex lanes by 256 / vlanes slot groups, vlanes a multiple of the wave size,
 // so a wave's slot is uniform; a thread keeps one vertex in registers and loops over its group's slots.
-template <int K, bool NRM, int MODE, class Tile>
+// tg: the tangent tier's planes and output; such a thread also keeps the base tangent, w in one register across the slot loop.
+template <int K, int TIER, int MODE, class Tile>
 __device__ __forceinline__ void skin_block(const Tile &t, float *skin_lds, int B, int V, int P, int S, int chunk, int vshift,
 		const float4 *__restrict__ m_pos, const float4 *__restrict__ m_nrm, const uint2 *__restrict__ m_idx,
 		const float4 *__restrict__ m_wgt, const float4 *__restrict__ m_spos, const float4 *__restrict__ m_snrm, int64_t wplane,
-		const float *__restrict__ skin, const float *__restrict__ shape_weights, float *__restrict__ out_p, float *__restrict__ out_n) {
-	constexpr bool kShaped = MODE != kNoShapes;
+		const float *__restrict__ skin, const float *__restrict__ shape_weights, float *__restrict__ out_p, float *__restrict__ out_n,
+		const SkinTangents tg = SkinTangents{}) {
+	constexpr bool kShaped = MODE != kNoShapes, NRM = TIER >= SKIN_NORMALS, TAN = TIER >= SKIN_TANGENTS;
 	const int v0 = (int)min((int64_t)blockIdx.y * chunk, (int64_t)V);
 	const int v1 = (int)min((int64_t)v0 + chunk, (int64_t)V);
 	if (t.slots() <= 0 || v0 >= v1) return;
@@ -152,19 +178,24 @@ __device__ __forceinline__ void skin_block(const Tile &t, float *skin_lds, int B
 	for (int v = v0 + vt; v < v1; v += vlanes) {
 		const SkinVertex<K> x = skin_load_vertex<K, NRM>(m_pos, m_nrm, m_idx, m_wgt, wplane, v);
 		const float4 *const sp = kShaped ? m_spos + v : nullptr, *const sn = kShaped && NRM ? m_snrm + v : nullptr;
+		float4 t4 = make_float4(0, 0, 0, 0);
+		if constexpr (TAN) t4 = tg.m_tan[v];
+		const float4 *st = nullptr;
+		if constexpr (kShaped && TAN) st = tg.m_stan + v;
 		for (int s = sg; s < t.slots(); s += sgroups) {
 			const int e = t.entry_of(s);
 			if (t.skipped(e)) continue;
-			V3 pos = x.pos, nrm = x.nrm;
-			if constexpr (kShaped) skin_shape_vertex<NRM, MODE>(P, wlds + s * P, sp, sn, wplane, pos, nrm);
+			V3 pos = x.pos, nrm = x.nrm, tan = v3(t4.x, t4.y, t4.z);
+			if constexpr (kShaped) skin_shape_vertex<TIER, MODE>(P, wlds + s * P, sp, sn, st, wplane, pos, nrm, tan);
 			// K matrix reads from the slot's LDS image, the blend, the transform, one 12-byte store an output
 			const float4 *ms = lds4 + s * B * 3;
 			X3 m = skin_scaled(skin_load_lds(ms + x.q[0]), x.w[0]);
 #pragma unroll
 			for (int k = 1; k < K; k++) m = skin_accumulate(m, skin_load_lds(ms + x.q[k]), x.w[k]);
-			const int64_t at = (t.row(s, e) * V + v) * 3;
+			const int64_t rv = t.row(s, e) * V + v, at = rv * 3;
 			skin_store3(out_p + at, skin_position(m, pos));
 			if constexpr (NRM) skin_store3(out_n + at, skin_normal(m, nrm));
+			if constexpr (TAN) skin_store4(tg.out_t + rv * 4, skin_normal(m, tan), t4.w);
 		}
 	}
 }
@@ -173,58 +204,70 @@ __device__ __forceinline__ void skin_block(const Tile &t, float *skin_lds, int B
 template <int N>
 using SkinInt = std::integral_constant<int, N>;
 
-// The one K x normals x mode ladder: f(K, NRM, MODE) with the three as integral constants.
-// mode: kNoShapes or a MorphMode.
+// The one K x tier x mode ladder: f(K, TIER, MODE) with the three as integral constants.
+// tier: a SkinTier; mode: kNoShapes or a MorphMode.
 template <class F>
-void skin_dispatch(int K, bool nrm, int mode, F f) {
+void skin_dispatch(int K, int tier, int mode, F f) {
 	const auto with_mode = [&](auto k, auto n) {
 		if (mode == kNoShapes) f(k, n, SkinInt<kNoShapes>());
 		else if (mode == MORPH_NORMALIZED) f(k, n, SkinInt<MORPH_NORMALIZED>());
 		else f(k, n, SkinInt<MORPH_RELATIVE>());
 	};
-	const auto with_nrm = [&](auto k) {
-		if (nrm) with_mode(k, std::true_type());
-		else with_mode(k, std::false_type());
+	const auto with_tier = [&](auto k) {
+		if (tier == SKIN_TANGENTS) with_mode(k, SkinInt<SKIN_TANGENTS>());
+		else if (tier == SKIN_NORMALS) with_mode(k, SkinInt<SKIN_NORMALS>());
+		else with_mode(k, SkinInt<SKIN_POSITIONS>());
 	};
-	if (K == 4) with_nrm(SkinInt<4>());
-	else with_nrm(SkinInt<8>());
+	if (K == 4) with_tier(SkinInt<4>());
+	else with_tier(SkinInt<8>());
 }
 
-// Kernels::kernel<K, NRM, MODE>() is a TU's __global__ entry point.  Every one of them may use the
+// Kernels::kernel<K, TIER, MODE>() is a TU's __global__ entry point.  Every one of them may use the
 // whole LDS (each TU, once, before its first launch).
 template <class Kernels>
 void skin_set_lds_limits() {
 	for (int K : {4, 8})
-		for (bool nrm : {false, true})
+		for (int tier : {(int)SKIN_POSITIONS, (int)SKIN_NORMALS, (int)SKIN_TANGENTS})
 			for (int mode : {kNoShapes, (int)MORPH_RELATIVE, (int)MORPH_NORMALIZED})
-				skin_dispatch(K, nrm, mode, [](auto k, auto n, auto m) {
+				skin_dispatch(K, tier, mode, [](auto k, auto n, auto m) {
 					(void)hipFuncSetAttribute((const void *)Kernels::template kernel<decltype(k)::value, decltype(n)::value, decltype(m)::value>(),
 							hipFuncAttributeMaxDynamicSharedMemorySize, kSkinMaxLdsBytes);
 				});
 }
 
 // The launch of `a` (kernels.h) over ceil(tiled / a.S) tiles x a.chunks vertex chunks: shaped when a.shape_weights is
-// given, normals when a.out_n is.  A TU's entry points take the plain or the shaped argument list, then `extra`, then the outputs.
+// given, normals when a.out_n is, tangents when a.out_t is.  A TU's entry points take the plain or the shaped argument
+// list, then `extra`, then the outputs; the tangent tier's have the tangent planes behind the normals' and out_t last.
 template <class Kernels, class... Extra>
 hipError_t skin_launch(const SkinLaunch &a, int64_t tiled, Extra... extra) {
 	const bool shaped = a.shape_weights != nullptr;
 	const SkinLayout l = skin_layout(a.V, a.K, a.mesh_normals);
 	const MorphLayout ml = morph_layout(a.V, a.K, a.mesh_normals, shaped ? a.P : 0); // (its stride is every plane's)
+	const TangentLayout tl = tangent_layout(a.V, a.K, a.mesh_normals, a.P, a.mesh_tangents); // (behind all the mesh's shapes)
+	if (a.out_t && (!a.out_n || !a.mesh_tangents)) return hipErrorInvalidValue;
 	const dim3 grid((unsigned)((tiled + a.S - 1) / a.S), (unsigned)a.chunks);
 	const size_t lds = (size_t)a.S * (size_t)morph_lds_bytes(a.B, shaped ? a.P : 0);
 	const auto plane = [&](bool have, int64_t at) { return have ? reinterpret_cast<const float4 *>(a.mesh + at) : nullptr; };
-	skin_dispatch(a.K, a.out_n != nullptr, shaped ? a.mode : kNoShapes, [&](auto k, auto n, auto m) {
-		constexpr bool NRM = decltype(n)::value;
+	skin_dispatch(a.K, skin_tier(a.out_n != nullptr, a.out_t != nullptr), shaped ? a.mode : kNoShapes, [&](auto k, auto n, auto m) {
+		constexpr int TIER = decltype(n)::value;
+		constexpr bool NRM = TIER >= SKIN_NORMALS, TAN = TIER >= SKIN_TANGENTS;
 		constexpr int MODE = decltype(m)::value;
-		const auto kernel = Kernels::template kernel<decltype(k)::value, NRM, MODE>();
+		const auto kernel = Kernels::template kernel<decltype(k)::value, TIER, MODE>();
 		const auto idx = reinterpret_cast<const uint2 *>(a.mesh + l.idx);
-		if constexpr (MODE == kNoShapes)
+		if constexpr (MODE == kNoShapes && !TAN)
 			hipLaunchKernelGGL(kernel, grid, dim3(kSkinThreads), lds, a.st, a.count, a.B, a.V, a.S, a.chunk, a.vshift, plane(true, l.pos),
 					plane(NRM, l.nrm), idx, plane(true, l.wgt), ml.stride, a.skin, extra..., a.out_p, a.out_n);
-		else
+		else if constexpr (!TAN)
 			hipLaunchKernelGGL(kernel, grid, dim3(kSkinThreads), lds, a.st, a.count, a.B, a.V, a.P, a.S, a.chunk, a.vshift, plane(true, l.pos),
 					plane(NRM, l.nrm), idx, plane(true, l.wgt), plane(true, ml.pos), plane(NRM, ml.nrm), ml.stride, a.skin, a.shape_weights,
 					extra..., a.out_p, a.out_n);
+		else if constexpr (MODE == kNoShapes)
+			hipLaunchKernelGGL(kernel, grid, dim3(kSkinThreads), lds, a.st, a.count, a.B, a.V, a.S, a.chunk, a.vshift, plane(true, l.pos),
+					plane(true, l.nrm), plane(true, tl.tan), idx, plane(true, l.wgt), ml.stride, a.skin, extra..., a.out_p, a.out_n, a.out_t);
+		else
+			hipLaunchKernelGGL(kernel, grid, dim3(kSkinThreads), lds, a.st, a.count, a.B, a.V, a.P, a.S, a.chunk, a.vshift, plane(true, l.pos),
+					plane(true, l.nrm), plane(true, tl.tan), idx, plane(true, l.wgt), plane(true, ml.pos), plane(true, ml.nrm),
+					plane(true, tl.stan), ml.stride, a.skin, a.shape_weights, extra..., a.out_p, a.out_n, a.out_t);
 	});
 	return hipGetLastError();
 }

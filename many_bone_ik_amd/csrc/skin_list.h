@@ -30,21 +30,26 @@ inline int32_t skin_list_length(const int32_t *list_count, int32_t max_list) { r
 // A checked mesh (and checked shapes when shape_weights is given; P, mode, shape_positions and
 // shape_normals are not looked at otherwise); skin [count][B][12], shape_weights [count][P] or null,
 // indices [max_list], list_count [1]; out_positions / out_normals [compact ? max_list : count][V][3].
+// out_tangents (the same rows, [V][4]) with the mesh's tangents [V][4], and shape_tangents when
+// shape_weights is given, or null.
 inline void skin_vertices_listed_host(int32_t B, int32_t V, int32_t K, const float *positions, const float *normals,
 		const int32_t *bone_indices, const float *weights, int32_t P, int32_t mode, const float *shape_positions,
 		const float *shape_normals, int32_t count, const int32_t *indices, const int32_t *list_count, int32_t max_list, const float *skin,
-		const float *shape_weights, bool compact, float *out_positions, float *out_normals) {
+		const float *shape_weights, bool compact, float *out_positions, float *out_normals, const float *tangents = nullptr,
+		const float *shape_tangents = nullptr, float *out_tangents = nullptr) {
 	const int32_t n = skin_list_length(list_count, max_list);
 	for (int64_t r = 0; r < n; r++) {
 		const int64_t s = indices[r];
 		if (s < 0 || s >= count) continue;
 		const int64_t at = (compact ? r : s) * V * 3;
 		float *out_n = out_normals ? out_normals + at : nullptr;
+		float *out_t = out_tangents ? out_tangents + (compact ? r : s) * V * 4 : nullptr;
 		if (shape_weights)
 			morph_skin_vertices_host(B, V, K, positions, normals, bone_indices, weights, P, mode, shape_positions, shape_normals, 1,
-					skin + s * B * 12, shape_weights + s * P, out_positions + at, out_n);
+					skin + s * B * 12, shape_weights + s * P, out_positions + at, out_n, tangents, shape_tangents, out_t);
 		else
-			skin_vertices_host(B, V, K, positions, normals, bone_indices, weights, 1, skin + s * B * 12, out_positions + at, out_n);
+			skin_vertices_host(B, V, K, positions, normals, bone_indices, weights, 1, skin + s * B * 12, out_positions + at, out_n, tangents,
+					out_t);
 	}
 }
 

@@ -26,6 +26,13 @@ Distance LOD lists: `Mesh.cull_lod()` writes one such list per 
 (mbik_cull_lod: Godot's visibility_range_begin / _end with their margins as hysteresis, in front of the
 plane test), `cull_lod_cpu()` is the host side, and `MeshLod` holds one mesh per level of detail:
 `select()` makes the lists and `skin()` skins each level's mesh over its own.
+
+Tangents: a `Mesh` created with `tangents` [V][4] (xyz and the binormal sign; with
+`shape_tangents` [P][V][3] on a shaped mesh) goes through mbik_mesh_create_desc, and `out_tangents_ptr` on
+`Mesh.skin()`, `Mesh.skin_listed()` and `MeshLod.skin()` writes the third stream [rows][V][4] through
+mbik_skin_vertices_call, the one struct-based call over the three forms (`Mesh.skin_call()` is that call
+as it is).  `skin_vertices_cpu(..., tangents=...)` and `skin_vertices_listed_cpu(..., tangents=...)` are
+the host sides; `synthetic_tangents()` and `synthetic_shape_tangents()` the seeded generators.
 """
 from __future__ import annotations
 
@@ -70,13 +77,38 @@ def _shape_arrays(V, shape_positions, shape_normals, shape_mode):
     return sh, (sp, sn)
 
 
+def _tangent_arrays(V, nrm, tangents, shapes, shape_tangents):
+    """-> (tangents [V][4] or None, shape_tangents [P][V][3] or None), contiguous float32."""
+    tan = None if tangents is None else np.ascontiguousarray(tangents, np.float32)
+    stan = None if shape_tangents is None else np.ascontiguousarray(shape_tangents, np.float32)
+    assert tan is None or tan.shape == (V, 4), tan.shape
+    assert stan is None or shapes is None or stan.shape == (shapes.shape_count, V, 3), stan.shape
+    return tan, stan
+
+
+def _mesh_desc(bone_count, pos, idx, wgt, nrm, tan, shapes, stan):
+    """mbik_mesh_desc over arrays the caller keeps alive."""
+    return _lib.MbikMeshDesc(C.sizeof(_lib.MbikMeshDesc), int(bone_count), pos.shape[0], idx.shape[1], _ptr(pos), _ptr(nrm), _ptr(tan),
+                             _ptr(idx), _ptr(wgt), None if shapes is None else C.pointer(shapes), _ptr(stan))
+
+
+def _skin_call(count, skin, out_positions, out_normals=None, out_tangents=None, shape_weights=None, indices=None, list_count=None,
+               max_list=0, flags=0):
+    """mbik_skin_call from addresses (ints, c_void_p or None)."""
+    vp = lambda x: x if isinstance(x, C.c_void_p) else C.c_void_p(x or None)
+    return _lib.MbikSkinCall(C.sizeof(_lib.MbikSkinCall), count, vp(skin), vp(shape_weights), vp(indices), vp(list_count), max_list, flags,
+                             vp(out_positions), vp(out_normals), vp(out_tangents))
+
+
 class Mesh:
     """One mesh surface on one GPU (mbik_mesh_create).  Immutable; close() frees it."""
 
     def __init__(self, bone_count: int, positions, bone_indices, weights, normals=None, device: int = 0,
-                 shape_positions=None, shape_normals=None, shape_mode: str = "relative"):
+                 shape_positions=None, shape_normals=None, shape_mode: str = "relative", tangents=None, shape_tangents=None):
         """shape_positions [P][V][3] (and shape_normals, exactly when `normals` is given) make a
-        shaped mesh (mbik_mesh_create_shaped); shape_mode is 'relative' or 'normalized'."""
+        shaped mesh (mbik_mesh_create_shaped); shape_mode is 'relative' or 'normalized'.  tangents
+        [V][4] (xyz and the binormal sign; needs normals; with shape_tangents [P][V][3] exactly when
+        the mesh is shaped) make a mesh with tangents (mbik_mesh_create_desc)."""
         self._L = _lib.load()
         pos, idx, wgt, nrm = _mesh_arrays(positions, bone_indices, weights, normals)
         self.bone_count, self.vertex_count, self.influences = int(bone_count), pos.shape[0], idx.shape[1]
@@ -84,8 +116,13 @@ class Mesh:
         self.device = device
         shapes, _keep = _shape_arrays(pos.shape[0], shape_positions, shape_normals, shape_mode)
         self.shape_count = 0 if shapes is None else shapes.shape_count
+        tan, stan = _tangent_arrays(pos.shape[0], nrm, tangents, shapes, shape_tangents)
+        self.has_tangents = tan is not None
         h = C.c_void_p()
-        if shapes is None:
+        if tan is not None or stan is not None:
+            desc = _mesh_desc(self.bone_count, pos, idx, wgt, nrm, tan, shapes, stan)
+            check(self._L.mbik_mesh_create_desc(C.byref(desc), device, C.byref(h)))
+        elif shapes is None:
             check(self._L.mbik_mesh_create(self.bone_count, self.vertex_count, self.influences, _ptr(pos), _ptr(nrm), _ptr(idx),
                                            _ptr(wgt), device, C.byref(h)))
         else:
@@ -93,12 +130,26 @@ class Mesh:
                                                   _ptr(idx), _ptr(wgt), C.byref(shapes), device, C.byref(h)))
         self.h = h
 
+    def skin_call(self, skin_ptr: int, out_positions_ptr: int, count: int, out_normals_ptr: int = 0, out_tangents_ptr: int = 0,
+                  shape_weights_ptr: int = 0, indices_ptr: int = 0, list_count_ptr: int = 0, max_list: int | None = None,
+                  compact: bool = False, stream: int = 0) -> None:
+        """mbik_skin_vertices_call: the plain (no list, no shape weights), the shaped or, with indices_ptr and
+        list_count_ptr, the listed form; out_tangents [rows][vertices][4] is the third stream of a mesh with
+        tangents, and without it the call is the existing entry of its form."""
+        call = _skin_call(count, skin_ptr, out_positions_ptr, out_normals_ptr, out_tangents_ptr, shape_weights_ptr, indices_ptr,
+                          list_count_ptr, count if max_list is None else max_list, _lib.SKIN_LIST_COMPACT if compact else 0)
+        check(self._L.mbik_skin_vertices_call(self.h, C.byref(call), C.c_void_p(stream or None)))
+
     def skin(self, skin_ptr: int, out_positions_ptr: int, count: int, out_normals_ptr: int = 0, stream: int = 0,
-             shape_weights_ptr: int = 0) -> None:
+             shape_weights_ptr: int = 0, out_tangents_ptr: int = 0) -> None:
         """mbik_skin_vertices: out_positions [count][vertices][3] (and out_normals) from the device
         skin transforms [count][bones][12]; asynchronous on `stream`.  With shape_weights_ptr (device,
         [count][shapes]) mbik_skin_vertices_shaped: each skeleton morphed by its own weights first;
-        without it a shaped mesh skins its base arrays."""
+        without it a shaped mesh skins its base arrays.  With out_tangents_ptr ([count][vertices][4])
+        mbik_skin_vertices_call writes the tangents as well."""
+        if out_tangents_ptr:
+            self.skin_call(skin_ptr, out_positions_ptr, count, out_normals_ptr, out_tangents_ptr, shape_weights_ptr, stream=stream)
+            return
         if shape_weights_ptr:
             check(self._L.mbik_skin_vertices_shaped(self.h, count, C.c_void_p(skin_ptr or None), C.c_void_p(shape_weights_ptr),
                                                     C.c_void_p(out_positions_ptr or None), C.c_void_p(out_normals_ptr or None),
@@ -150,12 +201,17 @@ class Mesh:
 
     def skin_listed(self, skin_ptr: int, out_positions_ptr: int, count: int, indices_ptr: int, list_count_ptr: int,
                     max_list: int | None = None, compact: bool = False, out_normals_ptr: int = 0, shape_weights_ptr: int = 0,
-                    stream: int = 0) -> None:
+                    stream: int = 0, out_tangents_ptr: int = 0) -> None:
         """mbik_skin_vertices_listed: skin() for the skeletons the device list indices [max_list] int32
         names, its length read from list_count [1] int32 on the device (cull()'s indices and
         visible_count on the same stream are such a list); max_list defaults to `count`.  An entry
         outside [0, count) is skipped.  In place the outputs are [count][vertices][3] and unlisted rows
-        are not touched; compact they are [max_list][vertices][3] and row r belongs to indices[r]."""
+        are not touched; compact they are [max_list][vertices][3] and row r belongs to indices[r].
+        out_tangents_ptr: the same rows of [vertices][4] (mbik_skin_vertices_call)."""
+        if out_tangents_ptr:
+            self.skin_call(skin_ptr, out_positions_ptr, count, out_normals_ptr, out_tangents_ptr, shape_weights_ptr, indices_ptr,
+                           list_count_ptr, max_list, compact, stream)
+            return
         check(self._L.mbik_skin_vertices_listed(self.h, count, C.c_void_p(indices_ptr or None), C.c_void_p(list_count_ptr or None),
                                                 count if max_list is None else max_list, C.c_void_p(skin_ptr or None),
                                                 C.c_void_p(shape_weights_ptr or None), _lib.SKIN_LIST_COMPACT if compact else 0,
@@ -188,11 +244,29 @@ class Mesh:
 
 
 def skin_vertices_cpu(bone_count: int, positions, bone_indices, weights, skin, normals=None, shape_positions=None,
-                      shape_normals=None, shape_mode: str = "relative", shape_weights=None):
+                      shape_normals=None, shape_mode: str = "relative", shape_weights=None, tangents=None, shape_tangents=None):
     """mbik_skin_vertices_cpu (host only): `skin` [count][bones][12] -> (positions [count][V][3],
     normals [count][V][3] or None when the mesh has none).  With shape_positions [P][V][3] (and
-    shape_normals) and shape_weights [count][P]: mbik_skin_vertices_shaped_cpu."""
+    shape_normals) and shape_weights [count][P]: mbik_skin_vertices_shaped_cpu.  With tangents [V][4]
+    (and shape_tangents [P][V][3] on a shaped mesh): mbik_skin_vertices_call_cpu, and a third array,
+    tangents [count][V][4]."""
     L = _lib.load()
+    if tangents is not None or shape_tangents is not None:
+        pos, idx, wgt, nrm = _mesh_arrays(positions, bone_indices, weights, normals)
+        sk = np.ascontiguousarray(skin, np.float32)
+        count, V = sk.shape[0], pos.shape[0]
+        assert sk.shape == (count, bone_count, 12), sk.shape
+        shapes, _keep = _shape_arrays(V, shape_positions, shape_normals, shape_mode)
+        tan, stan = _tangent_arrays(V, nrm, tangents, shapes, shape_tangents)
+        cw = None if shape_weights is None else np.ascontiguousarray(shape_weights, np.float32)
+        assert cw is None or shapes is None or cw.shape == (count, shapes.shape_count), cw.shape
+        out_p = np.empty((count, V, 3), np.float32)
+        out_n = None if nrm is None else np.empty((count, V, 3), np.float32)
+        out_t = None if tan is None else np.empty((count, V, 4), np.float32)
+        desc = _mesh_desc(bone_count, pos, idx, wgt, nrm, tan, shapes, stan)
+        call = _skin_call(count, _ptr(sk), _ptr(out_p), _ptr(out_n), _ptr(out_t), _ptr(cw))
+        check(L.mbik_skin_vertices_call_cpu(C.byref(desc), C.byref(call)))
+        return out_p, out_n, out_t
     pos, idx, wgt, nrm = _mesh_arrays(positions, bone_indices, weights, normals)
     sk = np.ascontiguousarray(skin, np.float32)
     count, V = sk.shape[0], pos.shape[0]
@@ -217,13 +291,16 @@ def skin_vertices_cpu(bone_count: int, positions, bone_indices, weights, skin, n
 
 def skin_vertices_listed_cpu(bone_count: int, positions, bone_indices, weights, skin, indices, list_count, max_list=None,
                              compact: bool = False, normals=None, shape_positions=None, shape_normals=None,
-                             shape_mode: str = "relative", shape_weights=None, out_positions=None, out_normals=None):
+                             shape_mode: str = "relative", shape_weights=None, out_positions=None, out_normals=None, tangents=None,
+                             shape_tangents=None, out_tangents=None):
     """mbik_skin_vertices_listed_cpu (host only): the skeletons indices[0 .. min(max(list_count, 0),
     max_list)) of `skin` [count][bones][12] -> (positions, normals or None when the mesh has none),
     [max_list][V][3] when compact and [count][V][3] otherwise.  max_list defaults to len(indices).  Rows
     the call does not write keep what out_positions / out_normals (float32 arrays of that shape, written
     in place) held; NaN when they are not given.  shape_weights [count][P] with shape_positions: the
-    shaped bits; shape_positions alone: the base arrays."""
+    shaped bits; shape_positions alone: the base arrays.  With tangents [V][4] (and shape_tangents on a
+    shaped mesh): mbik_skin_vertices_call_cpu, and a third array, tangents [rows][V][4] (out_tangents
+    as the other two)."""
     L = _lib.load()
     pos, idx, wgt, nrm = _mesh_arrays(positions, bone_indices, weights, normals)
     sk = np.ascontiguousarray(skin, np.float32)
@@ -244,6 +321,17 @@ def skin_vertices_listed_cpu(bone_count: int, positions, bone_indices, weights, 
     if shape_weights is not None:
         cw = np.ascontiguousarray(shape_weights, np.float32)
         assert shapes is None or cw.shape == (count, shapes.shape_count), cw.shape
+    if tangents is not None or shape_tangents is not None:
+        tan, stan = _tangent_arrays(V, nrm, tangents, shapes, shape_tangents)
+        out_t = out_tangents
+        if out_t is None and tan is not None:
+            out_t = np.full((rows, V, 4), np.nan, np.float32)
+        assert out_t is None or (out_t.dtype == np.float32 and out_t.shape == (rows, V, 4) and out_t.flags.c_contiguous)
+        desc = _mesh_desc(bone_count, pos, idx, wgt, nrm, tan, shapes, stan)
+        call = _skin_call(count, _ptr(sk), _ptr(outs[0]), _ptr(outs[1]), _ptr(out_t), _ptr(cw), _ptr(ind), _ptr(cnt), max_list,
+                          _lib.SKIN_LIST_COMPACT if compact else 0)
+        check(L.mbik_skin_vertices_call_cpu(C.byref(desc), C.byref(call)))
+        return outs[0], outs[1], out_t
     check(L.mbik_skin_vertices_listed_cpu(bone_count, V, idx.shape[1], _ptr(pos), _ptr(nrm), _ptr(idx), _ptr(wgt),
                                           None if shapes is None else C.byref(shapes), count, _ptr(ind), _ptr(cnt), max_list, _ptr(sk),
                                           _ptr(cw), _lib.SKIN_LIST_COMPACT if compact else 0, _ptr(outs[0]), _ptr(outs[1])))
@@ -347,15 +435,16 @@ class MeshLod:
                                 flags=_lib.LOD_EXCLUSIVE if exclusive else 0, stream=stream)
 
     def skin(self, skin_ptr: int, out_positions_ptrs, count: int, indices_ptr: int, list_counts_ptr: int, max_lists=None,
-             compact: bool = False, out_normals_ptrs=None, stream: int = 0) -> None:
+             compact: bool = False, out_normals_ptrs=None, stream: int = 0, out_tangents_ptrs=None) -> None:
         """skin_listed() once per level: meshes[r] over row r of select()'s indices ([ranges][count] int32)
         with list_counts[r], into out_positions_ptrs[r] (and out_normals_ptrs[r]).  max_lists[r] is the
-        caller's bound on list r's length (it sizes that launch); `count` where not given."""
+        caller's bound on list r's length (it sizes that launch); `count` where not given.
+        out_tangents_ptrs[r]: level r's tangents (its mesh has tangents), or 0 / None for none."""
         for r, mesh in enumerate(self.meshes):
             bound = count if max_lists is None else int(max_lists[r])
             mesh.skin_listed(skin_ptr, out_positions_ptrs[r], count, indices_ptr + 4 * r * count, list_counts_ptr + 4 * r,
                              max_list=bound, compact=compact, out_normals_ptr=0 if out_normals_ptrs is None else out_normals_ptrs[r],
-                             stream=stream)
+                             stream=stream, out_tangents_ptr=0 if out_tangents_ptrs is None else (out_tangents_ptrs[r] or 0))
 
 
 def synthetic_mesh(parents, rest_globals, vertex_count: int, influences: int, seed: int):
@@ -420,3 +509,30 @@ def synthetic_shapes(positions, normals, shape_count: int, seed: int):
     d /= np.maximum(np.linalg.norm(d, axis=2, keepdims=True), 1e-12)
     sn = (d * rng.uniform(0.0, 0.1, (P, V, 1))).astype(np.float32)
     return sp, sn
+
+
+def synthetic_tangents(positions, normals, seed: int):
+    """Seeded tangents for a mesh: [V][4], xyz a unit vector perpendicular to the vertex's normal (a random
+    direction with its normal component removed) and w the binormal sign, +1 or -1."""
+    nrm = np.asarray(normals, np.float64)
+    V = np.asarray(positions).shape[0]
+    assert nrm.shape == (V, 3), nrm.shape
+    rng = np.random.default_rng(seed)
+    n = nrm / np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-12)
+    d = rng.normal(0.0, 1.0, (V, 3))
+    t = d - n * (d * n).sum(axis=1, keepdims=True)
+    # (a direction along the normal leaves nothing: take the normal's cross product with its least axis instead)
+    axis = np.eye(3)[np.argmin(np.abs(n), axis=1)] if V else np.zeros((0, 3))
+    t = np.where(np.linalg.norm(t, axis=1, keepdims=True) < 1e-6, np.cross(n, axis), t)
+    t /= np.maximum(np.linalg.norm(t, axis=1, keepdims=True), 1e-12)
+    sign = np.where(rng.uniform(0.0, 1.0, (V, 1)) < 0.5, -1.0, 1.0)
+    return np.concatenate([t, sign], axis=1).astype(np.float32)
+
+
+def synthetic_shape_tangents(tangents, shape_count: int, seed: int):
+    """Seeded tangent offsets of dense blend shapes: [P][V][3], magnitude at most 0.1 as synthetic_shapes' normals."""
+    V, P = np.asarray(tangents).shape[0], int(shape_count)
+    rng = np.random.default_rng(seed)
+    d = rng.normal(0.0, 1.0, (P, V, 3))
+    d /= np.maximum(np.linalg.norm(d, axis=2, keepdims=True), 1e-12)
+    return (d * rng.uniform(0.0, 0.1, (P, V, 1))).astype(np.float32)
