@@ -571,6 +571,96 @@ int32_t mbik_clip_sample_layers(mbik_clipset *set, int32_t count, int32_t layer_
 int32_t mbik_clip_sample_layers_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
 		int32_t libm_variant, int32_t count, int32_t layer_count, const mbik_clip_layer *layers, uint32_t flags, float *pose_out);
 
+/* Blend-shape tracks of a clip set: the [count][shape_count] weights mbik_skin_vertices_shaped and
+ * mbik_skin_vertices_call read, written on the device from the times, clip indices and layer
+ * records that already drive the bones.  In Godot the same Animation resource carries
+ * TYPE_BLEND_SHAPE tracks beside its position / rotation / scale tracks, AnimationMixer blends
+ * them in the same pass and MeshInstance3D.set_blend_shape_value receives the result; here a
+ * shaped set carries them beside its mbik_clip_desc array (as mbik_mesh_create_shaped carries
+ * shapes beside a mesh), and two calls write the weights.  Purely additive to ABI 15: new symbols
+ * and new structs only, MBIK_ABI_VERSION stays 15; a caller detects the feature by the symbol
+ * mbik_clip_sample_shapes.
+ *
+ * mbik_clipset_create_shaped makes mbik_clipset_create's checks on its first arguments and builds
+ * the same set: mbik_clip_sample and mbik_clip_sample_layers on it give the bits they give on a
+ * set made by mbik_clipset_create.  bone_count == 0 (a face-only rig) is valid.  shapes->clips is
+ * parallel to `clips`: entry c holds the shape tracks of clip c, which shares that clip's length
+ * and loop_mode.  A shape without keys in a clip is untracked there.  Additional MBIK_EINVAL: a
+ * null shapes; struct_size < sizeof(mbik_clipset_shapes); shape_count < 1; a null shapes->clips; a
+ * negative track_count or a null tracks with tracks; a shape outside [0, shape_count); two tracks
+ * with keys for the same shape in one clip; an unknown interpolation; a negative key_count; key
+ * times that are not strictly increasing, not finite or outside [0, length]; a null times or
+ * values with key_count > 0.  Key values and init are taken as given, non-finite ones included.
+ *
+ * Semantics -- the _cpu entries are the specification, modelled on Godot 4.3's
+ * Animation::blend_shape_track_interpolate and the TYPE_BLEND_SHAPE case of
+ * AnimationMixer::_blend_process.  P = shape_count, I_j = init[j] (+0 for a NULL init).
+ * mbik_clip_sample_shapes, for skeleton s and shape j, is mbik_clip_sample's steps 1 to 6 with
+ * "shape" for "(bone, channel)" and I_j's bits for the rest pose:
+ *   1. clip_index[s] outside [0, clip_count): all P weights of the skeleton are 0x7fc00000; no
+ *      table is read.
+ *   2. t not finite: a tracked shape is 0x7fc00000, no key is read; an untracked shape as 4.
+ *   3. t' exactly as mbik_clip_sample's step 3.
+ *   4. An untracked shape: I_j's bits.
+ *   5. A tracked shape: the key i, the keys a and b, delta, from and c exactly as mbik_clip_sample's
+ *      step 5.  Nearest, or a pick without a second key: V[a]'s bits.  Linear:
+ *      V[a] + (V[b] - V[a]) * c (Math::lerp), float32, unfused.
+ *   6. A NaN produced by the arithmetic of 5 is stored as 0x7fc00000; copied bits stay as they are.
+ * mbik_clip_sample_shapes_layers is mbik_clip_sample_layers' steps 1 to 6 with I = I_j and the
+ * position / scale rule: a layer with clip == -1 is off; any other clip outside the set makes all
+ * P weights of the skeleton 0x7fc00000, decided by the kernel before any table access, and for any
+ * record array the verdict is the one mbik_clip_sample_layers gives; w is clamped into [0, 1]
+ * (a NaN passes); a layer contributes to shape j when its clip has keys for j; blend_l = w_l, or
+ * with MBIK_CLIP_LAYERS_NORMALIZE w_l / total over the contributing layers, a |total| <
+ * CMP_EPSILON giving the shape nothing; acc = I_j, and per contributing layer, ascending, unless
+ * |blend_l| < CMP_EPSILON (the layer is skipped, none of its keys read):
+ *        acc = acc + (x - I_j) * blend_l,   x = the shape's value by steps 2 to 6 above;
+ * a shape that had a layer accumulated stores acc, a NaN as 0x7fc00000; every other shape stores
+ * I_j's bits.  With K = 1 and w = 1 the result is I + (x - I) * 1, not the bits of the plain call.
+ * Not covered, as for the poses: cubic interpolation, ping-pong, backward playback, key
+ * transitions (ease), per-track filters, additive layers.
+ *
+ * The sample calls: device buffers on the set's device, asynchronous on hip_stream; time,
+ * clip_index and layers are read by the kernel only, never by the host.  MBIK_EINVAL: a null set; a
+ * set without shapes; then mbik_clip_sample's / mbik_clip_sample_layers' checks with weights_out
+ * for pose_out, and weights_out overlapping time, clip_index or layers.  count == 0 returns
+ * MBIK_OK without a launch.  weights_out needs float alignment only (time 8 bytes, layers 8
+ * bytes); element offsets are 64-bit; more than 2^39 weights a call is MBIK_EUNSUPPORTED. */
+typedef struct mbik_shape_track {
+	int32_t shape;           /* [0, shape_count) */
+	int32_t interpolation;   /* 0 nearest, 1 linear */
+	int32_t loop_wrap;       /* Animation track loop_wrap */
+	int32_t key_count;       /* 0 allowed: same as no track */
+	const double *times;     /* [key_count], mbik_clip_track's rules against the clip's length */
+	const float *values;     /* [key_count] */
+} mbik_shape_track;
+typedef struct mbik_clip_shape_tracks {
+	int32_t track_count;
+	const mbik_shape_track *tracks;
+} mbik_clip_shape_tracks;
+typedef struct mbik_clipset_shapes {
+	int32_t struct_size;     /* sizeof(mbik_clipset_shapes) */
+	int32_t shape_count;     /* P >= 1 */
+	const float *init;       /* [P], the RESET value of each shape; NULL: all +0 */
+	const mbik_clip_shape_tracks *clips; /* [clip_count], parallel to the mbik_clip_desc array */
+} mbik_clipset_shapes;
+int32_t mbik_clipset_create_shaped(int32_t bone_count, const float *rest_pose /* [bones][10] */, int32_t clip_count,
+		const mbik_clip_desc *clips, const mbik_clipset_shapes *shapes, int32_t libm_variant, int32_t device, mbik_clipset **out);
+int32_t mbik_clip_sample_shapes(mbik_clipset *set, int32_t count, const double *time /* device [count] */,
+		const int32_t *clip_index /* device [count], or NULL */, int32_t clip /* used when clip_index is NULL */,
+		float *weights_out /* device [count][P] */, void *hip_stream);
+int32_t mbik_clip_sample_shapes_layers(mbik_clipset *set, int32_t count, int32_t layer_count,
+		const mbik_clip_layer *layers /* device [count][layer_count] */, uint32_t flags, float *weights_out /* device [count][P] */,
+		void *hip_stream);
+/* Host-only (no device needed): the same arithmetic from the same code on host buffers, with
+ * mbik_clipset_create_shaped's and the sample calls' checks. */
+int32_t mbik_clip_sample_shapes_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		const mbik_clipset_shapes *shapes, int32_t libm_variant, int32_t count, const double *time, const int32_t *clip_index,
+		int32_t clip, float *weights_out);
+int32_t mbik_clip_sample_shapes_layers_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		const mbik_clipset_shapes *shapes, int32_t libm_variant, int32_t count, int32_t layer_count, const mbik_clip_layer *layers,
+		uint32_t flags, float *weights_out);
+
 /* Linear blend skinning of a mesh from skin transforms (ABI 10): what mbik_pose_globals' skinned
  * output exists for, on the device and on the stream of the solve.  The semantics are those of
  * Godot's skeleton compute shader -- blend the bone matrices, then transform -- on the ArrayMesh

@@ -35,7 +35,9 @@ EXPORTED_SYMBOLS = (
     "mbik_solve", "mbik_solve_checked", "mbik_solve_host", "mbik_segment_solve", "mbik_plan_segment_table", "mbik_describe_topology",
     "mbik_plan_step_classes", "mbik_describe_step_classes",
     "mbik_group_create", "mbik_group_solve", "mbik_group_destroy", "mbik_multi_create", "mbik_multi_solve",
-    "mbik_multi_skeletons", "mbik_multi_destroy", "mbik_capture_targets", "mbik_pose_globals", "mbik_pose_globals_cpu", "mbik_pose_blend", "mbik_pose_blend_cpu", "mbik_clipset_create", "mbik_clipset_destroy", "mbik_clip_sample", "mbik_clip_sample_cpu", "mbik_clip_sample_layers", "mbik_clip_sample_layers_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
+    "mbik_multi_skeletons", "mbik_multi_destroy", "mbik_capture_targets", "mbik_pose_globals", "mbik_pose_globals_cpu", "mbik_pose_blend", "mbik_pose_blend_cpu", "mbik_clipset_create", "mbik_clipset_destroy", "mbik_clip_sample", "mbik_clip_sample_cpu", "mbik_clip_sample_layers", "mbik_clip_sample_layers_cpu",
+    "mbik_clipset_create_shaped", "mbik_clip_sample_shapes", "mbik_clip_sample_shapes_layers", "mbik_clip_sample_shapes_cpu",
+    "mbik_clip_sample_shapes_layers_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
     "mbik_skin_vertices", "mbik_skin_vertices_cpu", "mbik_mesh_launch_shape", "mbik_mesh_create_shaped", "mbik_skin_vertices_shaped",
     "mbik_skin_vertices_shaped_cpu", "mbik_mesh_bone_boxes", "mbik_bone_boxes_cpu", "mbik_skin_bounds", "mbik_skin_bounds_cpu",
     "mbik_cull_boxes", "mbik_cull_boxes_cpu", "mbik_cull_lod", "mbik_cull_lod_cpu", "mbik_skin_vertices_listed", "mbik_skin_vertices_listed_cpu",
@@ -100,6 +102,20 @@ class MbikClipLayer(C.Structure):
 # mbik_clip_sample_layers: the most layers a skeleton can have, and its flag
 CLIP_MAX_LAYERS = 8
 CLIP_LAYERS_NORMALIZE = 1
+
+
+class MbikShapeTrack(C.Structure):
+    _fields_ = [("shape", C.c_int32), ("interpolation", C.c_int32), ("loop_wrap", C.c_int32), ("key_count", C.c_int32),
+                ("times", C.c_void_p), ("values", C.c_void_p)]
+
+
+class MbikClipShapeTracks(C.Structure):
+    _fields_ = [("track_count", C.c_int32), ("tracks", C.POINTER(MbikShapeTrack))]
+
+
+class MbikClipsetShapes(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("shape_count", C.c_int32), ("init", C.c_void_p),
+                ("clips", C.POINTER(MbikClipShapeTracks))]
 
 
 class MbikMeshShapes(C.Structure):
@@ -284,6 +300,19 @@ def load():
     L.mbik_clip_sample_layers_cpu.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MbikClipDesc), C.c_int32, C.c_int32, C.c_int32, vp,
                                               C.c_uint32, vp]
     L.mbik_clip_sample_layers_cpu.restype = C.c_int32
+    L.mbik_clipset_create_shaped.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MbikClipDesc), C.POINTER(MbikClipsetShapes), C.c_int32,
+                                             C.c_int32, C.POINTER(vp)]
+    L.mbik_clipset_create_shaped.restype = C.c_int32
+    L.mbik_clip_sample_shapes.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp]
+    L.mbik_clip_sample_shapes.restype = C.c_int32
+    L.mbik_clip_sample_shapes_layers.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_uint32, vp, vp]
+    L.mbik_clip_sample_shapes_layers.restype = C.c_int32
+    L.mbik_clip_sample_shapes_cpu.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MbikClipDesc), C.POINTER(MbikClipsetShapes), C.c_int32,
+                                              C.c_int32, vp, vp, C.c_int32, vp]
+    L.mbik_clip_sample_shapes_cpu.restype = C.c_int32
+    L.mbik_clip_sample_shapes_layers_cpu.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MbikClipDesc), C.POINTER(MbikClipsetShapes),
+                                                     C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, vp]
+    L.mbik_clip_sample_shapes_layers_cpu.restype = C.c_int32
     L.mbik_mesh_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.POINTER(vp)]
     L.mbik_mesh_create.restype = C.c_int32
     L.mbik_mesh_destroy.argtypes = [vp]

@@ -12,6 +12,13 @@ host form.
 A clip is a dict: {"length": seconds, "loop_mode": 0 none | 1 linear, "tracks": [track, ...]}; a
 track is a dict: {"bone", "channel": 0 position | 1 rotation | 2 scale, "interpolation": 0 nearest |
 1 linear, "loop_wrap": 0 | 1, "times": [keys] float64, "values": [keys][3 or 4] float32}.
+
+A clip may also carry blend-shape tracks: "shape_tracks": [{"shape", "interpolation",
+"loop_wrap", "times": [keys] float64, "values": [keys] float32}, ...].  A `ClipSet` made with
+`shape_count` > 0 holds them; `ClipSet.sample_shapes()` and `ClipSet.sample_shapes_layers()` write
+the [count][shape_count] weights `Mesh.skin(..., shape_weights_ptr=...)` reads, from the same times,
+clip indices and layer records as the poses.  `clip_sample_shapes_cpu()` and
+`clip_sample_shapes_layers_cpu()` are the host forms, `synthetic_shape_tracks()` the seeded generator.
 """
 from __future__ import annotations
 
@@ -63,6 +70,37 @@ def _descs(clips):
     return descs, keep
 
 
+def _shape_descs(shape_count, clips, shape_init):
+    """(mbik_clipset_shapes, the objects its pointers refer to) from the clips' "shape_tracks"."""
+    keep = []
+    per_clip = (_lib.MbikClipShapeTracks * max(len(clips), 1))()
+    for d, clip in zip(per_clip, clips):
+        tracks = clip.get("shape_tracks", [])
+        arr = (_lib.MbikShapeTrack * max(len(tracks), 1))()
+        for t, tr in zip(arr, tracks):
+            times = None if tr.get("times") is None else np.ascontiguousarray(tr["times"], np.float64).reshape(-1)
+            values = None if tr.get("values") is None else np.ascontiguousarray(tr["values"], np.float32).reshape(-1)
+            n = tr.get("key_count", 0 if times is None else times.shape[0])
+            if values is not None and times is not None and "key_count" not in tr:
+                assert values.size == n, (values.shape, n)
+            keep += [times, values]
+            t.shape, t.interpolation = int(tr["shape"]), int(tr.get("interpolation", LINEAR))
+            t.loop_wrap, t.key_count = int(tr.get("loop_wrap", 1)), int(n)
+            t.times = None if times is None else times.ctypes.data
+            t.values = None if values is None else values.ctypes.data
+        keep.append(arr)
+        d.track_count = int(clip.get("shape_track_count", len(tracks)))
+        d.tracks = C.cast(arr, C.POINTER(_lib.MbikShapeTrack)) if tracks or "shape_track_count" not in clip else None
+    init = None if shape_init is None else np.ascontiguousarray(shape_init, np.float32).reshape(-1)
+    assert init is None or init.shape == (shape_count,), init.shape
+    sh = _lib.MbikClipsetShapes()
+    sh.struct_size, sh.shape_count = C.sizeof(_lib.MbikClipsetShapes), int(shape_count)
+    sh.init = None if init is None else init.ctypes.data
+    sh.clips = C.cast(per_clip, C.POINTER(_lib.MbikClipShapeTracks))
+    keep += [per_clip, init]
+    return sh, keep
+
+
 def _rest(bone_count, rest_pose):
     rest = np.ascontiguousarray(rest_pose, np.float32)
     assert rest.shape == (bone_count, 10), rest.shape
@@ -72,13 +110,21 @@ def _rest(bone_count, rest_pose):
 class ClipSet:
     """Several clips of one rig on one GPU (mbik_clipset_create).  Immutable; close() frees it."""
 
-    def __init__(self, bone_count: int, rest_pose, clips, libm_variant: int = 0, device: int = 0):
+    def __init__(self, bone_count: int, rest_pose, clips, libm_variant: int = 0, device: int = 0, shape_count: int = 0,
+                 shape_init=None):
         self._L = _lib.load()
         rest = _rest(bone_count, rest_pose)
         descs, keep = _descs(clips)
         self.bone_count, self.clip_count, self.libm_variant, self.device = int(bone_count), len(clips), libm_variant, device
+        self.shape_count = int(shape_count)
         h = C.c_void_p()
-        check(self._L.mbik_clipset_create(self.bone_count, _ptr(rest), len(clips), descs, libm_variant, device, C.byref(h)))
+        if self.shape_count == 0:
+            check(self._L.mbik_clipset_create(self.bone_count, _ptr(rest), len(clips), descs, libm_variant, device, C.byref(h)))
+        else:
+            sh, keep_sh = _shape_descs(self.shape_count, clips, shape_init)
+            check(self._L.mbik_clipset_create_shaped(self.bone_count, _ptr(rest), len(clips), descs, C.byref(sh), libm_variant, device,
+                                                     C.byref(h)))
+            del keep_sh
         del keep
         self.h = h
 
@@ -94,6 +140,20 @@ class ClipSet:
         LAYERS_NORMALIZE for AnimationPlayer's cross-fade); asynchronous on `stream`."""
         check(self._L.mbik_clip_sample_layers(self.h, count, layer_count, C.c_void_p(layers_ptr or None), flags,
                                               C.c_void_p(pose_out_ptr or None), C.c_void_p(stream or None)))
+
+    def sample_shapes(self, time_ptr: int, weights_out_ptr: int, count: int, clip_index_ptr: int = 0, clip: int = 0,
+                      stream: int = 0) -> None:
+        """mbik_clip_sample_shapes: weights_out [count][shape_count] (float32, what Mesh.skin's
+        shape_weights_ptr reads) from the device arrays sample() takes; asynchronous on `stream`."""
+        check(self._L.mbik_clip_sample_shapes(self.h, count, C.c_void_p(time_ptr or None), C.c_void_p(clip_index_ptr or None), clip,
+                                              C.c_void_p(weights_out_ptr or None), C.c_void_p(stream or None)))
+
+    def sample_shapes_layers(self, layers_ptr: int, weights_out_ptr: int, count: int, layer_count: int, flags: int = 0,
+                             stream: int = 0) -> None:
+        """mbik_clip_sample_shapes_layers: weights_out [count][shape_count] from the layer records
+        sample_layers() takes, blended as AnimationMixer blends blend-shape tracks; asynchronous on `stream`."""
+        check(self._L.mbik_clip_sample_shapes_layers(self.h, count, layer_count, C.c_void_p(layers_ptr or None), flags,
+                                                     C.c_void_p(weights_out_ptr or None), C.c_void_p(stream or None)))
 
     def close(self) -> None:
         if getattr(self, "h", None):
@@ -155,6 +215,48 @@ def clip_sample_layers_cpu(bone_count: int, rest_pose, clips, layers, flags: int
     check(L.mbik_clip_sample_layers_cpu(bone_count, _ptr(rest), len(clips), descs, libm_variant, rec.shape[0], rec.shape[1], _ptr(rec),
                                         flags, _ptr(out)))
     del keep
+    return out
+
+
+# the host forms of the shape calls need no rig: the pose tracks of `clips` are left out
+_NO_REST = np.zeros((1, 10), np.float32)
+
+
+def _shape_only(clips):
+    return [dict(length=c["length"], loop_mode=c.get("loop_mode", LOOP_NONE), tracks=[],
+                 **{k: c[k] for k in ("shape_tracks", "shape_track_count") if k in c}) for c in clips]
+
+
+def clip_sample_shapes_cpu(shape_count: int, clips, time, clip_index=None, clip: int = 0, shape_init=None):
+    """mbik_clip_sample_shapes_cpu (host only): `time` [count] seconds and `clip_index` [count] (or
+    the one `clip`) -> weights [count][shape_count]."""
+    L = _lib.load()
+    clips = _shape_only(clips)
+    descs, keep = _descs(clips)
+    sh, keep_sh = _shape_descs(shape_count, clips, shape_init)
+    t = np.ascontiguousarray(time, np.float64).reshape(-1)
+    idx = None if clip_index is None else np.ascontiguousarray(clip_index, np.int32).reshape(-1)
+    assert idx is None or idx.shape == t.shape, (idx.shape, t.shape)
+    out = np.empty((t.shape[0], max(int(shape_count), 0)), np.float32)
+    check(L.mbik_clip_sample_shapes_cpu(0, _ptr(_NO_REST), len(clips), descs, C.byref(sh), 0, t.shape[0], _ptr(t), _ptr(idx), clip,
+                                        _ptr(out)))
+    del keep, keep_sh
+    return out
+
+
+def clip_sample_shapes_layers_cpu(shape_count: int, clips, layers, flags: int = 0, shape_init=None):
+    """mbik_clip_sample_shapes_layers_cpu (host only): `layers` [count][K] of LAYER_DTYPE
+    (pack_layers) -> weights [count][shape_count]."""
+    L = _lib.load()
+    clips = _shape_only(clips)
+    descs, keep = _descs(clips)
+    sh, keep_sh = _shape_descs(shape_count, clips, shape_init)
+    rec = np.ascontiguousarray(layers, LAYER_DTYPE)
+    assert rec.ndim == 2, rec.shape
+    out = np.empty((rec.shape[0], max(int(shape_count), 0)), np.float32)
+    check(L.mbik_clip_sample_shapes_layers_cpu(0, _ptr(_NO_REST), len(clips), descs, C.byref(sh), 0, rec.shape[0], rec.shape[1],
+                                               _ptr(rec), flags, _ptr(out)))
+    del keep, keep_sh
     return out
 
 
@@ -228,3 +330,37 @@ def synthetic_clips(seed: int, bone_count: int, clip_count: int = 3, key_counts=
                                    times=times.astype(np.float64), values=values.astype(np.float32)))
         clips.append(dict(length=length, loop_mode=LOOP_LINEAR if c % 2 == 0 else LOOP_NONE, tracks=tracks))
     return rest, clips
+
+
+def synthetic_shape_tracks(seed: int, shape_count: int, clips, key_counts=(0, 1, 2, 3, 17)):
+    """Copies of `clips` with seeded "shape_tracks" for `shape_count` blend shapes added.
+
+    synthetic_clips' mix: every (clip, shape) draws its key count from `key_counts` (0: untracked),
+    its interpolation and its loop_wrap at random; a third of the tracks keep their keys strictly
+    inside (0, length), a third have keys exactly at 0 and at length, and a third a key at 0 only.
+    Values lie in [-0.25, 1.25]; about a tenth of them are exactly 0 and a tenth exactly 1."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for clip in clips:
+        length = float(clip["length"])
+        tracks = []
+        for shape in range(int(shape_count)):
+            n = int(key_counts[rng.integers(0, len(key_counts))])
+            interpolation, loop_wrap, edge = int(rng.integers(0, 2)), int(rng.integers(0, 2)), int(rng.integers(0, 3))
+            if n == 0:
+                continue
+            times = np.sort(rng.uniform(0.05 * length, 0.95 * length, n))
+            while n > 1 and np.min(np.diff(times)) <= 0.0:
+                times = np.sort(rng.uniform(0.05 * length, 0.95 * length, n))
+            if edge >= 1:
+                times[0] = 0.0
+            if edge == 1 and n > 1:
+                times[-1] = length
+            values = rng.uniform(-0.25, 1.25, n)
+            u = rng.uniform(0.0, 1.0, n)
+            values[u < 0.1] = 0.0
+            values[u > 0.9] = 1.0
+            tracks.append(dict(shape=shape, interpolation=interpolation, loop_wrap=loop_wrap, times=times.astype(np.float64),
+                               values=values.astype(np.float32)))
+        out.append(dict(clip, shape_tracks=tracks))
+    return out

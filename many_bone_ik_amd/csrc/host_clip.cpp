@@ -3,13 +3,16 @@
 // per-bone code (clip.h) on the host.  The front stage of a frame: the poses mbik_solve reads are
 // sampled on the solve's stream from a time and a clip index per skeleton.  DESIGN.md §16.
 // mbik_clip_sample_layers and its _cpu form blend up to 8 (time, clip, weight) layers a skeleton
-// the same way (k_clip_layers.hip, clip_layers.h).
+// the same way (k_clip_layers.hip, clip_layers.h).  A set made by
+// mbik_clipset_create_shaped carries blend-shape tracks as well: mbik_clip_sample_shapes and
+// mbik_clip_sample_shapes_layers write the [count][P] weights the shaped skinning reads
+// (k_clip_shapes.hip, clip_shapes.h).
 #include "host.h"
 
 #include <cmath>
 #include <cstddef>
 
-#include "clip_layers.h"
+#include "clip_shapes.h"
 
 using namespace mbik_host;
 
@@ -18,6 +21,9 @@ struct mbik_clipset {
 	int32_t B = 0, clip_count = 0, libm = 0;
 	DevBuf blob;
 	mbik::ClipView view{}; // device pointers into blob
+	int32_t P = 0;         // 0: a set without shapes
+	DevBuf shape_blob;
+	mbik::ShapeView shapes{}; // device pointers into shape_blob
 };
 
 namespace {
@@ -118,16 +124,103 @@ static_assert(sizeof(mbik_clip_layer) == sizeof(mbik::ClipLayer) && offsetof(mbi
 
 size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
-} // namespace
+// The repacked shape tracks (clip_shapes.h), checked.  `clips` has passed pack().
+struct PackedShapes {
+	std::vector<mbik::ClipInfo> clips;
+	std::vector<mbik::ShapeHeader> headers;
+	std::vector<mbik::ShapeKey> keys;
+	std::vector<float> init;
+	mbik::ShapeView view() const {
+		return mbik::ShapeView{(int32_t)init.size(), (int32_t)clips.size(), clips.data(), headers.data(), keys.data(), init.data()};
+	}
+};
 
-extern "C" {
+int pack_shapes(int32_t clip_count, const mbik_clip_desc *clips, const mbik_clipset_shapes *sh, PackedShapes &out) {
+	if (!sh) return fail(MBIK_EINVAL, "null shapes");
+	if (sh->struct_size < (int32_t)sizeof(mbik_clipset_shapes)) return fail(MBIK_EINVAL, "shapes->struct_size is smaller than mbik_clipset_shapes");
+	const int32_t P = sh->shape_count;
+	if (P < 1) return fail(MBIK_EINVAL, "shape_count must be at least 1");
+	if (!sh->clips) return fail(MBIK_EINVAL, "null shapes->clips");
+	if ((int64_t)clip_count * P > INT32_MAX) return fail(MBIK_EUNSUPPORTED, "more than 2^31 (clip, shape) headers");
+	out.clips.resize(clip_count);
+	out.headers.assign((size_t)clip_count * P, mbik::ShapeHeader{0, 0, 0, 0});
+	if (sh->init) out.init.assign(sh->init, sh->init + P);
+	else out.init.assign((size_t)P, 0.0f);
+	for (int32_t c = 0; c < clip_count; c++) {
+		const mbik_clip_desc &d = clips[c];
+		const mbik_clip_shape_tracks &st = sh->clips[c];
+		const std::string where = "clip " + std::to_string(c);
+		out.clips[c] = mbik::ClipInfo{d.length, d.loop_mode, 0};
+		if (st.track_count < 0) return fail(MBIK_EINVAL, where + ": negative shape track_count");
+		if (st.track_count > 0 && !st.tracks) return fail(MBIK_EINVAL, where + ": null shape tracks");
+		for (int32_t k = 0; k < st.track_count; k++) {
+			const mbik_shape_track &t = st.tracks[k];
+			const std::string tw = where + " shape track " + std::to_string(k);
+			if (t.shape < 0 || t.shape >= P) return fail(MBIK_EINVAL, tw + ": shape " + std::to_string(t.shape) + " outside [0, " + std::to_string(P) + ")");
+			if (t.interpolation != 0 && t.interpolation != 1) return fail(MBIK_EINVAL, tw + ": unknown interpolation " + std::to_string(t.interpolation));
+			if (t.key_count < 0) return fail(MBIK_EINVAL, tw + ": negative key_count");
+			if (t.key_count == 0) continue; // the same as no track
+			if (!t.times || !t.values) return fail(MBIK_EINVAL, tw + ": null times or values");
+			mbik::ShapeHeader &h = out.headers[(size_t)c * P + t.shape];
+			if (h.key_count) return fail(MBIK_EINVAL, tw + ": a second track with keys for shape " + std::to_string(t.shape));
+			if (out.keys.size() + (size_t)t.key_count > (size_t)INT32_MAX) return fail(MBIK_EUNSUPPORTED, "more than 2^31 shape keys in a clip set");
+			for (int32_t i = 0; i < t.key_count; i++) {
+				const double x = t.times[i];
+				if (!std::isfinite(x) || !(x >= 0) || !(x <= d.length))
+					return fail(MBIK_EINVAL, tw + ": key " + std::to_string(i) + " has a time that is not finite or outside [0, length]");
+				if (i > 0 && !(x > t.times[i - 1])) return fail(MBIK_EINVAL, tw + ": key times are not strictly increasing at key " + std::to_string(i));
+			}
+			h.key_off = (int32_t)out.keys.size(), h.key_count = t.key_count;
+			h.flags = (t.interpolation == 1 ? mbik::kClipLinear : 0) | (d.loop_mode == 1 && t.loop_wrap ? mbik::kClipWrap : 0);
+			for (int32_t i = 0; i < t.key_count; i++) out.keys.push_back(mbik::ShapeKey{t.times[i], t.values[i], 0.0f});
+		}
+	}
+	// the spare record that makes index key_off + 0 valid for every header (clip_shapes.h)
+	out.keys.push_back(mbik::ShapeKey{0.0, 0.0f, 0.0f});
+	return MBIK_OK;
+}
 
-int32_t mbik_clipset_create(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
-		int32_t libm_variant, int32_t device, mbik_clipset **out) {
+// The checks of the two shape sampling calls; 0 = go on, 1 = nothing to do.
+int check_shapes_call(int32_t P, int32_t clip_count, int32_t count, const double *time, const int32_t *clip_index, int32_t clip,
+		const float *weights_out) {
+	if (count < 0) return fail(MBIK_EINVAL, "negative count");
+	if (count == 0) return 1;
+	if (!time) return fail(MBIK_EINVAL, "null time");
+	if (!weights_out) return fail(MBIK_EINVAL, "null weights_out");
+	if (!clip_index && (clip < 0 || clip >= clip_count))
+		return fail(MBIK_EINVAL, "clip " + std::to_string(clip) + " outside the set's " + std::to_string(clip_count) + " clips");
+	const size_t bytes = (size_t)count * P * sizeof(float);
+	if (overlap(time, (size_t)count * sizeof(double), weights_out, bytes)) return fail(MBIK_EINVAL, "weights_out overlaps time");
+	if (clip_index && overlap(clip_index, (size_t)count * sizeof(int32_t), weights_out, bytes))
+		return fail(MBIK_EINVAL, "weights_out overlaps clip_index");
+	return 0;
+}
+
+int check_shapes_layers_call(int32_t P, int32_t count, int32_t layer_count, const mbik_clip_layer *layers, uint32_t flags,
+		const float *weights_out) {
+	if (count < 0) return fail(MBIK_EINVAL, "negative count");
+	if (layer_count < 1 || layer_count > MBIK_CLIP_MAX_LAYERS)
+		return fail(MBIK_EINVAL, "layer_count " + std::to_string(layer_count) + " outside [1, " + std::to_string(MBIK_CLIP_MAX_LAYERS) + "]");
+	if (flags & ~MBIK_CLIP_LAYERS_NORMALIZE) return fail(MBIK_EINVAL, "unknown flags " + std::to_string(flags));
+	if (count == 0) return 1;
+	if (!layers) return fail(MBIK_EINVAL, "null layers");
+	if (!weights_out) return fail(MBIK_EINVAL, "null weights_out");
+	if (reinterpret_cast<uintptr_t>(layers) % 8) return fail(MBIK_EINVAL, "layers is not 8-byte aligned");
+	if (overlap(layers, (size_t)count * layer_count * sizeof(mbik_clip_layer), weights_out, (size_t)count * P * sizeof(float)))
+		return fail(MBIK_EINVAL, "weights_out overlaps layers");
+	return 0;
+}
+
+// mbik_clipset_create, and with `shapes` mbik_clipset_create_shaped.
+int create_set(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips, bool shaped,
+		const mbik_clipset_shapes *shapes, int32_t libm_variant, int32_t device, mbik_clipset **out) {
 	if (!out) return fail(MBIK_EINVAL, "null out");
 	*out = nullptr;
 	Packed pk;
 	if (int rc = pack(bone_count, rest_pose, clip_count, clips, libm_variant, pk)) return rc;
+	PackedShapes ps;
+	if (shaped)
+		if (int rc = pack_shapes(clip_count, clips, shapes, ps)) return rc;
 	if (int rc = check_device(device)) return rc;
 	std::unique_ptr<mbik_clipset> s(new mbik_clipset());
 	s->device = device, s->B = bone_count, s->clip_count = clip_count, s->libm = libm_variant;
@@ -150,8 +243,42 @@ int32_t mbik_clipset_create(int32_t bone_count, const float *rest_pose, int32_t 
 	s->view = mbik::ClipView{bone_count, clip_count, reinterpret_cast<const mbik::ClipInfo *>(b + o_info),
 			reinterpret_cast<const mbik::ClipHeader *>(b + o_head), reinterpret_cast<const double *>(b + o_time),
 			reinterpret_cast<const mbik::ClipValue *>(b + o_val), reinterpret_cast<const float *>(b + o_rest)};
+	if (shaped) {
+		// a blob of its own: clip infos, headers, key records, init, each from a 16-byte boundary
+		const size_t m_info = ps.clips.size() * sizeof(mbik::ClipInfo), m_head = ps.headers.size() * sizeof(mbik::ShapeHeader),
+					 m_key = ps.keys.size() * sizeof(mbik::ShapeKey), m_init = ps.init.size() * sizeof(float);
+		const size_t p_info = 0, p_head = up16(p_info + m_info), p_key = up16(p_head + m_head), p_init = up16(p_key + m_key),
+					 total = up16(p_init + m_init) + 16;
+		std::vector<unsigned char> sb(total, 0);
+		std::memcpy(sb.data() + p_info, ps.clips.data(), m_info);
+		std::memcpy(sb.data() + p_head, ps.headers.data(), m_head);
+		std::memcpy(sb.data() + p_key, ps.keys.data(), m_key);
+		std::memcpy(sb.data() + p_init, ps.init.data(), m_init);
+		if (int rc = s->shape_blob.reserve(total, "hipMalloc failed for the clip set's shape tracks")) return rc;
+		unsigned char *d = s->shape_blob.as<unsigned char>();
+		if (hipMemcpy(d, sb.data(), total, hipMemcpyHostToDevice) != hipSuccess)
+			return fail(MBIK_EHIP, "hipMemcpy failed for the clip set's shape tracks");
+		s->P = (int32_t)ps.init.size();
+		s->shapes = mbik::ShapeView{s->P, clip_count, reinterpret_cast<const mbik::ClipInfo *>(d + p_info),
+				reinterpret_cast<const mbik::ShapeHeader *>(d + p_head), reinterpret_cast<const mbik::ShapeKey *>(d + p_key),
+				reinterpret_cast<const float *>(d + p_init)};
+	}
 	*out = s.release();
 	return MBIK_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t mbik_clipset_create(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		int32_t libm_variant, int32_t device, mbik_clipset **out) {
+	return create_set(bone_count, rest_pose, clip_count, clips, false, nullptr, libm_variant, device, out);
+}
+
+int32_t mbik_clipset_create_shaped(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		const mbik_clipset_shapes *shapes, int32_t libm_variant, int32_t device, mbik_clipset **out) {
+	return create_set(bone_count, rest_pose, clip_count, clips, true, shapes, libm_variant, device, out);
 }
 
 void mbik_clipset_destroy(mbik_clipset *s) { delete s; }
@@ -207,6 +334,65 @@ int32_t mbik_clip_sample_layers_cpu(int32_t bone_count, const float *rest_pose, 
 	for (int64_t s = 0; s < count; s++)
 		for (int32_t b = 0; b < bone_count; b++)
 			mbik::clip_layers_bone(v, L + s * layer_count, layer_count, flags, b, libm_variant, pose_out + (s * bone_count + b) * 10);
+	return MBIK_OK;
+}
+
+int32_t mbik_clip_sample_shapes(mbik_clipset *s, int32_t count, const double *time, const int32_t *clip_index, int32_t clip,
+		float *weights_out, void *hip_stream) {
+	if (!s) return fail(MBIK_EINVAL, "null clip set");
+	if (!s->P) return fail(MBIK_EINVAL, "the clip set has no shapes (mbik_clipset_create_shaped)");
+	const int rc = check_shapes_call(s->P, s->clip_count, count, time, clip_index, clip, weights_out);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	if ((int64_t)count * s->P > (int64_t)INT32_MAX * 256) return fail(MBIK_EUNSUPPORTED, "more than 2^39 weights in one call");
+	DeviceGuard guard(s->device);
+	hipError_t e = mbik::launch_clip_shapes(reinterpret_cast<hipStream_t>(hip_stream), s->shapes, (int64_t)count * s->P, time, clip_index,
+			clip, weights_out);
+	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("shape sample launch failed: ") + hipGetErrorString(e));
+	return MBIK_OK;
+}
+
+int32_t mbik_clip_sample_shapes_layers(mbik_clipset *s, int32_t count, int32_t layer_count, const mbik_clip_layer *layers, uint32_t flags,
+		float *weights_out, void *hip_stream) {
+	if (!s) return fail(MBIK_EINVAL, "null clip set");
+	if (!s->P) return fail(MBIK_EINVAL, "the clip set has no shapes (mbik_clipset_create_shaped)");
+	const int rc = check_shapes_layers_call(s->P, count, layer_count, layers, flags, weights_out);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	if ((int64_t)count * s->P > (int64_t)INT32_MAX * 256) return fail(MBIK_EUNSUPPORTED, "more than 2^39 weights in one call");
+	DeviceGuard guard(s->device);
+	hipError_t e = mbik::launch_clip_shapes_layers(reinterpret_cast<hipStream_t>(hip_stream), s->shapes, (int64_t)count * s->P,
+			reinterpret_cast<const mbik::ClipLayer *>(layers), layer_count, flags, weights_out);
+	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("layered shape sample launch failed: ") + hipGetErrorString(e));
+	return MBIK_OK;
+}
+
+int32_t mbik_clip_sample_shapes_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		const mbik_clipset_shapes *shapes, int32_t libm_variant, int32_t count, const double *time, const int32_t *clip_index, int32_t clip,
+		float *weights_out) {
+	Packed pk;
+	if (int rc = pack(bone_count, rest_pose, clip_count, clips, libm_variant, pk)) return rc;
+	PackedShapes ps;
+	if (int rc = pack_shapes(clip_count, clips, shapes, ps)) return rc;
+	const mbik::ShapeView v = ps.view();
+	const int rc = check_shapes_call(v.P, clip_count, count, time, clip_index, clip, weights_out);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	for (int64_t s = 0; s < count; s++)
+		for (int32_t j = 0; j < v.P; j++) weights_out[s * v.P + j] = mbik::shape_sample(v, clip_index ? clip_index[s] : clip, j, time[s]);
+	return MBIK_OK;
+}
+
+int32_t mbik_clip_sample_shapes_layers_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		const mbik_clipset_shapes *shapes, int32_t libm_variant, int32_t count, int32_t layer_count, const mbik_clip_layer *layers,
+		uint32_t flags, float *weights_out) {
+	Packed pk;
+	if (int rc = pack(bone_count, rest_pose, clip_count, clips, libm_variant, pk)) return rc;
+	PackedShapes ps;
+	if (int rc = pack_shapes(clip_count, clips, shapes, ps)) return rc;
+	const mbik::ShapeView v = ps.view();
+	const int rc = check_shapes_layers_call(v.P, count, layer_count, layers, flags, weights_out);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	const mbik::ClipLayer *L = reinterpret_cast<const mbik::ClipLayer *>(layers);
+	for (int64_t s = 0; s < count; s++)
+		for (int32_t j = 0; j < v.P; j++) weights_out[s * v.P + j] = mbik::shape_layers(v, L + s * layer_count, layer_count, flags, j);
 	return MBIK_OK;
 }
 

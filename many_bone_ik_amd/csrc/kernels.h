@@ -224,6 +224,13 @@ hipError_t launch_clip(hipStream_t st, const ClipView &v, int libm, int64_t tota
 struct ClipLayer;
 hipError_t launch_clip_layers(hipStream_t st, const ClipView &v, int libm, int64_t total_bones, const ClipLayer *layers, int layer_count,
 		uint32_t flags, float *pose_out);
+// k_clip_shapes.hip: mbik_clip_sample_shapes and mbik_clip_sample_shapes_layers (clip_shapes.h).  One thread per weight of the
+// total_weights = count * v.P, 256 weights a block, no LDS; the arguments otherwise as the two launches above.
+struct ShapeView;
+hipError_t launch_clip_shapes(hipStream_t st, const ShapeView &v, int64_t total_weights, const double *time, const int32_t *clip_index,
+		int clip, float *weights_out);
+hipError_t launch_clip_shapes_layers(hipStream_t st, const ShapeView &v, int64_t total_weights, const ClipLayer *layers, int layer_count,
+		uint32_t flags, float *weights_out);
 #ifdef MBIK_PROF
 // Diagnostic cycle accounting (-DMBIK_PROF): each kernel TU has its own counters; adds them to
 // out[24] and clears them.
