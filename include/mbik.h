@@ -546,8 +546,8 @@ int32_t mbik_clip_sample_cpu(int32_t bone_count, const float *rest_pose, int32_t
  * Deviations from Godot: step 2's clamp (Godot would extrapolate; the slerp's double sine needs its
  * argument in [0, pi/2], the reason mbik_pose_blend gives for clamping negative weights; additive
  * layers are out of scope).  init_* are the rest pose's ten floats as given (Godot derives them
- * from the rest Transform3D).  Per-track blend weights (filters), root motion, RESET animations
- * and post_process_key_value are not covered.
+ * from the rest Transform3D).  Per-track blend weights (filters), RESET animations and
+ * post_process_key_value are not covered.  Root motion is mbik_clip_root_motion_layers, below.
  *
  * MBIK_EINVAL: a null set; count < 0; layer_count outside [1, MBIK_CLIP_MAX_LAYERS]; unknown flag
  * bits; and, when there is work to do, a null layers or pose_out, layers not 8-byte aligned, or
@@ -570,6 +570,92 @@ int32_t mbik_clip_sample_layers(mbik_clipset *set, int32_t count, int32_t layer_
  * mbik_clipset_create's and mbik_clip_sample_layers' checks. */
 int32_t mbik_clip_sample_layers_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
 		int32_t libm_variant, int32_t count, int32_t layer_count, const mbik_clip_layer *layers, uint32_t flags, float *pose_out);
+
+/* Root motion: AnimationMixer's root_motion_track for a crowd.  Three stages of a frame take
+ * skeleton_global [count][12], each character's world transform; these calls produce it on the
+ * device.  Per skeleton, the extraction calls write the root bone's motion over the frame -- from
+ * the previous time to the time of each layer, with the loop seam handled -- into a motion record,
+ * hold the root bone at rest in the pose, and mbik_root_motion_apply composes the record into
+ * skeleton_global in place.  Purely additive to ABI 15: new symbols and one new flag, no existing
+ * struct or call changed, the sample calls keep their bits, MBIK_ABI_VERSION stays 15.  A caller
+ * detects the feature by the presence of the symbol mbik_clip_root_motion.
+ *
+ * A motion record is 10 floats in the pose record's order: the rotation delta x, y, z, w (what
+ * AnimationMixer::get_root_motion_rotation returns), the position delta
+ * (get_root_motion_position) and the scale delta (get_root_motion_scale).
+ *
+ * Semantics -- Godot's core is not part of the reference tree, so the _cpu entries are the
+ * specification, modelled on the root_motion branches of the position, rotation and scale cases of
+ * Godot 4.3's AnimationMixer::_blend_process.  mbik_clip_root_motion is defined as
+ * mbik_clip_root_motion_layers with one record (time[s], clip_index[s] or clip, 1.0f),
+ * time_prev[s] and flags 0; it is one code path and gives the same bits.  All arithmetic is
+ * float32 and unfused, in the order written.  For skeleton s, root bone r and each channel ch of
+ * r, K = layer_count:
+ *   1. Validity is mbik_clip_sample_layers' step 1: a layer with clip == -1 is off -- nothing of
+ *      it is used, its time_prev included.  Any other clip outside [0, clip_count) makes all 10
+ *      floats of the record 0x7fc00000; that is decided from the records before any table access,
+ *      and pose[s] is then left untouched.
+ *   2. w_l, the contributing layers, the channel's total and blend_l are exactly what
+ *      mbik_clip_sample_layers' steps 2 to 5 compute for bone r.  A layer is skipped without
+ *      reading a key when its clip does not track the channel or |blend_l| < CMP_EPSILON.
+ *   3. The segments of layer l, with t1 = layers[l].time, t0 = time_prev[l], L = the clip's length.
+ *      Both finite: p0 = t0 and p1 = t1 mapped by mbik_clip_sample's step 3; looped = (loop_mode
+ *      linear && p0 > p1), an exact double compare.  Not looped: one segment (p0, p1).  Looped:
+ *      two segments in this order, (p0, L) then (+0.0, p1).  Either time not finite: one segment
+ *      whose two values are both 0x7fc00000, and no key is read.
+ *   4. X(u) is the channel's value at the already mapped time u by mbik_clip_sample's steps 5 and
+ *      6; there is no second time mapping, so X(L) on a looping clip is the value at the end of
+ *      the clip, not the value at fposmod's 0.
+ *   5. Accumulation over the contributing layers, ascending, and each layer's segments (u0, u1) in
+ *      order, from position +0,+0,+0, scale +0,+0,+0 and rotation 0,0,0,1:
+ *        position, scale:  acc = acc + (X(u1) - X(u0)) * blend_l
+ *        rotation:         acc = normalized(acc * slerp(identity, inverse(X(u0)) * X(u1), blend_l))
+ *      with mbik_clip_sample_layers' slerp, inverse, quaternion product and normalized.
+ *   6. A channel that accumulated at least one segment stores acc, any NaN as 0x7fc00000; every
+ *      other channel stores its start value's bits.
+ *   7. With pose non-NULL, pose[s][r][0..9] of every valid skeleton is overwritten with the rest
+ *      pose's bits of bone r: Godot does not apply a root-motion track to the bone.  The call runs
+ *      behind the sample call that wrote pose, on the same stream.
+ * Deviations from Godot: forward playback only.  At most one wrap a frame is seen, as in Godot: a
+ * frame longer than the clip loses whole loops.  On a LOOP_NONE clip p0 > p1 is a plain negative
+ * difference.
+ *
+ * mbik_root_motion_apply, per skeleton: G = skeleton_global[s], basis rows then origin as in
+ * mbik_capture_targets; q = the record's rotation, p = its position; the scale delta is not
+ * applied.  G' = G * Transform3D(Basis(q), p) as Transform3D::operator*= computes it: origin' =
+ * G.xform(p), basis' = G.basis * Basis(q) (Basis::set_quaternion, Basis::operator*).  With
+ * MBIK_ROOT_MOTION_ORTHONORMALIZE basis' = basis'.orthonormalized(): a long walk otherwise drifts
+ * off orthonormal.  Any NaN is stored as 0x7fc00000; non-finite input propagates.  The set names
+ * the device only.
+ *
+ * MBIK_EINVAL: a null set; count < 0; root_bone outside [0, bone_count), so a set without bones is
+ * always invalid here; layer_count outside [1, MBIK_CLIP_MAX_LAYERS]; unknown flag bits; a plain
+ * `clip` outside the set when clip_index is NULL; and, when count > 0, a null required buffer
+ * (pose and clip_index may be NULL), layers, time or time_prev not 8-byte aligned, motion_out
+ * overlapping any input or pose, skeleton_global overlapping motion.  count == 0 returns MBIK_OK
+ * without a launch.  Device buffers on the set's device, asynchronous on hip_stream; layers, the
+ * times and clip_index are read by the kernel only, which tests every clip index before any table
+ * access.  motion_out, pose and skeleton_global need float alignment. */
+#define MBIK_ROOT_MOTION_ORTHONORMALIZE 1u
+int32_t mbik_clip_root_motion(mbik_clipset *set, int32_t count, int32_t root_bone,
+		const double *time_prev /* device [count] */, const double *time /* device [count] */,
+		const int32_t *clip_index /* device [count], or NULL */, int32_t clip,
+		float *motion_out /* device [count][10] */, float *pose /* device [count][bones][10], or NULL */, void *hip_stream);
+int32_t mbik_clip_root_motion_layers(mbik_clipset *set, int32_t count, int32_t layer_count, int32_t root_bone,
+		const mbik_clip_layer *layers /* device [count][layer_count], this frame's records */,
+		const double *time_prev /* device [count][layer_count] */, uint32_t flags /* MBIK_CLIP_LAYERS_NORMALIZE */,
+		float *motion_out, float *pose, void *hip_stream);
+int32_t mbik_root_motion_apply(mbik_clipset *set, int32_t count, const float *motion /* device [count][10] */,
+		uint32_t flags, float *skeleton_global /* device [count][12], in place */, void *hip_stream);
+/* Host-only (no device needed): the same arithmetic from the same code on host buffers, with
+ * mbik_clipset_create's checks and the checks above. */
+int32_t mbik_clip_root_motion_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		int32_t libm_variant, int32_t count, int32_t root_bone, const double *time_prev, const double *time,
+		const int32_t *clip_index, int32_t clip, float *motion_out, float *pose);
+int32_t mbik_clip_root_motion_layers_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		int32_t libm_variant, int32_t count, int32_t layer_count, int32_t root_bone, const mbik_clip_layer *layers,
+		const double *time_prev, uint32_t flags, float *motion_out, float *pose);
+int32_t mbik_root_motion_apply_cpu(int32_t count, const float *motion, uint32_t flags, float *skeleton_global);
 
 /* Blend-shape tracks of a clip set: the [count][shape_count] weights mbik_skin_vertices_shaped and
  * mbik_skin_vertices_call read, written on the device from the times, clip indices and layer

@@ -37,7 +37,8 @@ EXPORTED_SYMBOLS = (
     "mbik_group_create", "mbik_group_solve", "mbik_group_destroy", "mbik_multi_create", "mbik_multi_solve",
     "mbik_multi_skeletons", "mbik_multi_destroy", "mbik_capture_targets", "mbik_pose_globals", "mbik_pose_globals_cpu", "mbik_pose_blend", "mbik_pose_blend_cpu", "mbik_clipset_create", "mbik_clipset_destroy", "mbik_clip_sample", "mbik_clip_sample_cpu", "mbik_clip_sample_layers", "mbik_clip_sample_layers_cpu",
     "mbik_clipset_create_shaped", "mbik_clip_sample_shapes", "mbik_clip_sample_shapes_layers", "mbik_clip_sample_shapes_cpu",
-    "mbik_clip_sample_shapes_layers_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
+    "mbik_clip_sample_shapes_layers_cpu", "mbik_clip_root_motion", "mbik_clip_root_motion_layers", "mbik_root_motion_apply",
+    "mbik_clip_root_motion_cpu", "mbik_clip_root_motion_layers_cpu", "mbik_root_motion_apply_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
     "mbik_skin_vertices", "mbik_skin_vertices_cpu", "mbik_mesh_launch_shape", "mbik_mesh_create_shaped", "mbik_skin_vertices_shaped",
     "mbik_skin_vertices_shaped_cpu", "mbik_mesh_bone_boxes", "mbik_bone_boxes_cpu", "mbik_skin_bounds", "mbik_skin_bounds_cpu",
     "mbik_cull_boxes", "mbik_cull_boxes_cpu", "mbik_cull_lod", "mbik_cull_lod_cpu", "mbik_skin_vertices_listed", "mbik_skin_vertices_listed_cpu",
@@ -102,6 +103,7 @@ class MbikClipLayer(C.Structure):
 # mbik_clip_sample_layers: the most layers a skeleton can have, and its flag
 CLIP_MAX_LAYERS = 8
 CLIP_LAYERS_NORMALIZE = 1
+ROOT_MOTION_ORTHONORMALIZE = 1  # MBIK_ROOT_MOTION_ORTHONORMALIZE
 
 
 class MbikShapeTrack(C.Structure):
@@ -313,6 +315,20 @@ def load():
     L.mbik_clip_sample_shapes_layers_cpu.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MbikClipDesc), C.POINTER(MbikClipsetShapes),
                                                      C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, vp]
     L.mbik_clip_sample_shapes_layers_cpu.restype = C.c_int32
+    L.mbik_clip_root_motion.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp]
+    L.mbik_clip_root_motion.restype = C.c_int32
+    L.mbik_clip_root_motion_layers.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_uint32, vp, vp, vp]
+    L.mbik_clip_root_motion_layers.restype = C.c_int32
+    L.mbik_root_motion_apply.argtypes = [vp, C.c_int32, vp, C.c_uint32, vp, vp]
+    L.mbik_root_motion_apply.restype = C.c_int32
+    L.mbik_clip_root_motion_cpu.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MbikClipDesc), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp,
+                                            C.c_int32, vp, vp]
+    L.mbik_clip_root_motion_cpu.restype = C.c_int32
+    L.mbik_clip_root_motion_layers_cpu.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MbikClipDesc), C.c_int32, C.c_int32, C.c_int32,
+                                                   C.c_int32, vp, vp, C.c_uint32, vp, vp]
+    L.mbik_clip_root_motion_layers_cpu.restype = C.c_int32
+    L.mbik_root_motion_apply_cpu.argtypes = [C.c_int32, vp, C.c_uint32, vp]
+    L.mbik_root_motion_apply_cpu.restype = C.c_int32
     L.mbik_mesh_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.POINTER(vp)]
     L.mbik_mesh_create.restype = C.c_int32
     L.mbik_mesh_destroy.argtypes = [vp]

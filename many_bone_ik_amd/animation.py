@@ -19,6 +19,13 @@ A clip may also carry blend-shape tracks: "shape_tracks": [{"sh
 the [count][shape_count] weights `Mesh.skin(..., shape_weights_ptr=...)` reads, from the same times,
 clip indices and layer records as the poses.  `clip_sample_shapes_cpu()` and
 `clip_sample_shapes_layers_cpu()` are the host forms, `synthetic_shape_tracks()` the seeded generator.
+
+Root motion: `ClipSet.root_motion()` / `ClipSet.root_motion_layers()` write one
+motion record [10] (rotation delta xyzw, position delta, scale delta of the root bone over the frame,
+the loop seam handled) per skeleton and hold the root bone at rest in the sampled poses;
+`ClipSet.apply_root_motion()` composes the records into skeleton_global [count][12] in place.
+`clip_root_motion_cpu()`, `clip_root_motion_layers_cpu()` and `root_motion_apply_cpu()` are the host
+forms, `synthetic_walk_clips()` the seeded generator of clips whose root bone walks and turns.
 """
 from __future__ import annotations
 
@@ -39,6 +46,7 @@ LAYER_DTYPE = np.dtype([("time", "<f8"), ("clip", "<i4"), ("weight", "<f4")])
 MAX_LAYERS = _lib.CLIP_MAX_LAYERS
 LAYERS_NORMALIZE = _lib.CLIP_LAYERS_NORMALIZE
 LAYER_OFF = -1
+ROOT_MOTION_ORTHONORMALIZE = _lib.ROOT_MOTION_ORTHONORMALIZE
 
 
 def _ptr(a):
@@ -155,6 +163,31 @@ class ClipSet:
         check(self._L.mbik_clip_sample_shapes_layers(self.h, count, layer_count, C.c_void_p(layers_ptr or None), flags,
                                                      C.c_void_p(weights_out_ptr or None), C.c_void_p(stream or None)))
 
+    def root_motion(self, time_prev_ptr: int, time_ptr: int, motion_out_ptr: int, count: int, root_bone: int, clip_index_ptr: int = 0,
+                    clip: int = 0, pose_ptr: int = 0, stream: int = 0) -> None:
+        """mbik_clip_root_motion: motion_out [count][10] -- the root bone's rotation, position and scale
+        deltas from time_prev [count] to time [count] (float64) in clip_index [count] (or the one
+        `clip`); with pose_ptr the root bone of the sampled poses [count][bones][10] is put back to
+        rest.  Asynchronous on `stream`, behind the sample call that wrote the poses."""
+        check(self._L.mbik_clip_root_motion(self.h, count, root_bone, C.c_void_p(time_prev_ptr or None), C.c_void_p(time_ptr or None),
+                                            C.c_void_p(clip_index_ptr or None), clip, C.c_void_p(motion_out_ptr or None),
+                                            C.c_void_p(pose_ptr or None), C.c_void_p(stream or None)))
+
+    def root_motion_layers(self, layers_ptr: int, time_prev_ptr: int, motion_out_ptr: int, count: int, layer_count: int, root_bone: int,
+                           flags: int = 0, pose_ptr: int = 0, stream: int = 0) -> None:
+        """mbik_clip_root_motion_layers: the same from this frame's layer records [count][layer_count]
+        (what sample_layers() took) and each layer's previous time [count][layer_count] (float64),
+        blended with sample_layers()' factors (flags: LAYERS_NORMALIZE)."""
+        check(self._L.mbik_clip_root_motion_layers(self.h, count, layer_count, root_bone, C.c_void_p(layers_ptr or None),
+                                                   C.c_void_p(time_prev_ptr or None), flags, C.c_void_p(motion_out_ptr or None),
+                                                   C.c_void_p(pose_ptr or None), C.c_void_p(stream or None)))
+
+    def apply_root_motion(self, motion_ptr: int, skeleton_global_ptr: int, count: int, flags: int = 0, stream: int = 0) -> None:
+        """mbik_root_motion_apply: skeleton_global [count][12] (basis rows, then origin) times each
+        record's Transform3D(Basis(rotation), position), in place (flags: ROOT_MOTION_ORTHONORMALIZE)."""
+        check(self._L.mbik_root_motion_apply(self.h, count, C.c_void_p(motion_ptr or None), flags, C.c_void_p(skeleton_global_ptr or None),
+                                             C.c_void_p(stream or None)))
+
     def close(self) -> None:
         if getattr(self, "h", None):
             self._L.mbik_clipset_destroy(self.h)
@@ -216,6 +249,61 @@ def clip_sample_layers_cpu(bone_count: int, rest_pose, clips, layers, flags: int
                                         flags, _ptr(out)))
     del keep
     return out
+
+
+def _pose_arg(pose, count, bone_count):
+    if pose is None:
+        return None
+    assert isinstance(pose, np.ndarray) and pose.dtype == np.float32 and pose.flags["C_CONTIGUOUS"], "pose is changed in place"
+    assert pose.shape == (count, bone_count, 10), pose.shape
+    return pose
+
+
+def clip_root_motion_cpu(bone_count: int, rest_pose, clips, time_prev, time, root_bone: int, clip_index=None, clip: int = 0, pose=None,
+                         libm_variant: int = 0):
+    """mbik_clip_root_motion_cpu (host only): `time_prev` and `time` [count] seconds and `clip_index`
+    [count] (or the one `clip`) -> motion records [count][10].  `pose` (float32 [count][bones][10],
+    optional) gets the rest pose's root record in place."""
+    L = _lib.load()
+    rest = _rest(bone_count, rest_pose)
+    descs, keep = _descs(clips)
+    t0 = np.ascontiguousarray(time_prev, np.float64).reshape(-1)
+    t1 = np.ascontiguousarray(time, np.float64).reshape(-1)
+    idx = None if clip_index is None else np.ascontiguousarray(clip_index, np.int32).reshape(-1)
+    assert t0.shape == t1.shape and (idx is None or idx.shape == t1.shape), (t0.shape, t1.shape)
+    out = np.empty((t1.shape[0], 10), np.float32)
+    check(L.mbik_clip_root_motion_cpu(bone_count, _ptr(rest), len(clips), descs, libm_variant, t1.shape[0], root_bone, _ptr(t0), _ptr(t1),
+                                      _ptr(idx), clip, _ptr(out), _ptr(_pose_arg(pose, t1.shape[0], bone_count))))
+    del keep
+    return out
+
+
+def clip_root_motion_layers_cpu(bone_count: int, rest_pose, clips, layers, time_prev, root_bone: int, flags: int = 0, pose=None,
+                                libm_variant: int = 0):
+    """mbik_clip_root_motion_layers_cpu (host only): `layers` [count][K] of LAYER_DTYPE and
+    `time_prev` [count][K] seconds -> motion records [count][10]; `pose` as in clip_root_motion_cpu."""
+    L = _lib.load()
+    rest = _rest(bone_count, rest_pose)
+    descs, keep = _descs(clips)
+    rec = np.ascontiguousarray(layers, LAYER_DTYPE)
+    assert rec.ndim == 2, rec.shape
+    t0 = np.ascontiguousarray(time_prev, np.float64).reshape(rec.shape)
+    out = np.empty((rec.shape[0], 10), np.float32)
+    check(L.mbik_clip_root_motion_layers_cpu(bone_count, _ptr(rest), len(clips), descs, libm_variant, rec.shape[0], rec.shape[1], root_bone,
+                                             _ptr(rec), _ptr(t0), flags, _ptr(out), _ptr(_pose_arg(pose, rec.shape[0], bone_count))))
+    del keep
+    return out
+
+
+def root_motion_apply_cpu(motion, skeleton_global, flags: int = 0):
+    """mbik_root_motion_apply_cpu (host only): a new skeleton_global [count][12] = each transform
+    times its record's Transform3D(Basis(rotation), position)."""
+    L = _lib.load()
+    m = np.ascontiguousarray(motion, np.float32).reshape(-1, 10)
+    g = np.array(skeleton_global, np.float32, order="C").reshape(-1, 12)
+    assert g.shape[0] == m.shape[0], (g.shape, m.shape)
+    check(L.mbik_root_motion_apply_cpu(m.shape[0], _ptr(m), flags, _ptr(g)))
+    return g
 
 
 # the host forms of the shape calls need no rig: the pose tracks of `clips` are left out
@@ -330,6 +418,41 @@ def synthetic_clips(seed: int, bone_count: int, clip_count: int = 3, key_counts=
                                    times=times.astype(np.float64), values=values.astype(np.float32)))
         clips.append(dict(length=length, loop_mode=LOOP_LINEAR if c % 2 == 0 else LOOP_NONE, tracks=tracks))
     return rest, clips
+
+
+def synthetic_walk_clips(seed: int, bone_count: int, root_bone: int, clip_count: int = 3, key_counts=(0, 1, 2, 3, 17),
+                         lengths=(1.0, 3.0), walk_keys=(2, 3, 9)):
+    """synthetic_clips' set with a walking root: (rest_pose, clips).
+
+    The tracks of `root_bone` are replaced, from a random stream of their own (seed + 1): in every
+    clip but the last a position track and a yaw-rotation track whose keys run from key 0 at time 0
+    (position 0, no turn) to a key at time `length` holding the net displacement (up to 2 units a
+    loop) and the net turn (up to 100 degrees about y); key counts come from `walk_keys`, and each
+    track draws its interpolation and its loop_wrap at random.  The first clip has a scale track of
+    the same shape as well.  The last clip leaves the root untracked.  Every other bone is
+    synthetic_clips' own."""
+    rest, clips = synthetic_clips(seed, bone_count, clip_count, key_counts, lengths)
+    rng = np.random.default_rng(seed + 1)
+    out = []
+    for c, clip in enumerate(clips):
+        length = float(clip["length"])
+        tracks = [t for t in clip["tracks"] if t["bone"] != root_bone]
+        if c < max(1, len(clips) - 1):
+            for channel in (POSITION, ROTATION, SCALE)[:3 if c == 0 else 2]:
+                n = int(walk_keys[rng.integers(0, len(walk_keys))])
+                times = np.concatenate([[0.0], np.sort(rng.uniform(0.05 * length, 0.95 * length, n - 2)), [length]])
+                f = times / length + np.concatenate([[0.0], rng.uniform(-0.3, 0.3, n - 2) / n, [0.0]])   # uneven pace
+                if channel == ROTATION:
+                    ang = np.radians(rng.uniform(-100.0, 100.0)) * f
+                    values = np.stack([np.zeros(n), np.sin(ang / 2), np.zeros(n), np.cos(ang / 2)], axis=1)
+                elif channel == POSITION:
+                    values = f[:, None] * rng.uniform(-2.0, 2.0, 3)[None, :]
+                else:
+                    values = 1.0 + f[:, None] * rng.uniform(-0.25, 0.25, 3)[None, :]
+                tracks.append(dict(bone=int(root_bone), channel=channel, interpolation=int(rng.integers(0, 2)),
+                                   loop_wrap=int(rng.integers(0, 2)), times=times.astype(np.float64), values=values.astype(np.float32)))
+        out.append(dict(clip, tracks=tracks))
+    return rest, out
 
 
 def synthetic_shape_tracks(seed: int, shape_count: int, clips, key_counts=(0, 1, 2, 3, 17)):

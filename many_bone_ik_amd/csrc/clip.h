@@ -171,42 +171,67 @@ struct ClipSampled {
 	V3 pos, scl;
 	bool has_pos, has_rot, has_scl;
 };
-// hp / hr / hs: the bone's three headers in `info`'s clip, already loaded -- a caller that samples
-// several clips loads the next one's while this one's keys are searched.  What a lane waits for is
-// memory, so the loads are arranged in as few dependent rounds as the data allows: the search
-// steps, three loads each; then the two key times and the two key values of all three channels at
-// once.
-GDI ClipSampled clip_sample_channels(const ClipView &v, const ClipInfo &info, const ClipHeader &hp, const ClipHeader &hr,
-		const ClipHeader &hs, double t, int lv) {
-	ClipChan pos = clip_chan(v, hp), rot = clip_chan(v, hr), scl = clip_chan(v, hs);
-	ClipSampled out;
-	out.has_pos = pos.n != 0, out.has_rot = rot.n != 0, out.has_scl = scl.n != 0;
-	if (!clip_finite(t)) { // no key is read
-		const float nan = clip_nan();
-		out.rot = q4(nan, nan, nan, nan), out.pos = v3(nan, nan, nan), out.scl = v3(nan, nan, nan);
-		return out;
-	}
-	const double tp = clip_time(t, info.length, info.loop_mode);
+// The three channels' searches for their last key <= tp, in step: pos ends as the count of keys <= tp.
+GDI void clip_search(ClipChan &pos, ClipChan &rot, ClipChan &scl, double tp) {
 	const int nrs = rot.n > scl.n ? rot.n : scl.n, nmax = pos.n > nrs ? pos.n : nrs;
 	int step = 1;
 	while (step <= (nmax >> 1)) step <<= 1; // the highest power of two <= nmax
 	for (; step > 0; step >>= 1) clip_search_step(pos, rot, scl, step, tp);
-	const ClipPick pp = clip_pick(pos), pr = clip_pick(rot), ps = clip_pick(scl);
-	// twelve independent loads
-	const double pTa = pos.T[pp.a], pTb = pos.T[pp.b], rTa = rot.T[pr.a], rTb = rot.T[pr.b], sTa = scl.T[ps.a], sTb = scl.T[ps.b];
-	const ClipValue pVa = pos.V[pp.a], pVb = pos.V[pp.b], rVa = rot.V[pr.a], rVb = rot.V[pr.b], sVa = scl.V[ps.a], sVb = scl.V[ps.b];
-	const float pc = clip_weight(pp.mode, pTa, pTb, tp, info.length), rc = clip_weight(pr.mode, rTa, rTb, tp, info.length),
-				sc = clip_weight(ps.mode, sTa, sTb, tp, info.length);
-	if (rot.n == 0 || pr.mode == kClipCopy) {
-		out.rot = q4(rVa.x, rVa.y, rVa.z, rVa.w);
+}
+// The picks of three searched channels, and the two key times and the two key values of each:
+// twelve independent loads.
+struct ClipLoaded {
+	ClipPick pp, pr, ps;
+	double pTa, pTb, rTa, rTb, sTa, sTb;
+	ClipValue pVa, pVb, rVa, rVb, sVa, sVb;
+};
+GDI ClipLoaded clip_load(const ClipChan &pos, const ClipChan &rot, const ClipChan &scl) {
+	ClipLoaded k;
+	k.pp = clip_pick(pos), k.pr = clip_pick(rot), k.ps = clip_pick(scl);
+	k.pTa = pos.T[k.pp.a], k.pTb = pos.T[k.pp.b], k.rTa = rot.T[k.pr.a], k.rTb = rot.T[k.pr.b], k.sTa = scl.T[k.ps.a], k.sTb = scl.T[k.ps.b];
+	k.pVa = pos.V[k.pp.a], k.pVb = pos.V[k.pp.b], k.rVa = rot.V[k.pr.a], k.rVb = rot.V[k.pr.b], k.sVa = scl.V[k.ps.a], k.sVb = scl.V[k.ps.b];
+	return k;
+}
+// Steps 5 and 6 from the loaded keys; rot_n is the rotation channel's key count.
+GDI void clip_eval(const ClipLoaded &k, int rot_n, double tp, double length, int lv, ClipSampled &out) {
+	const float pc = clip_weight(k.pp.mode, k.pTa, k.pTb, tp, length), rc = clip_weight(k.pr.mode, k.rTa, k.rTb, tp, length),
+				sc = clip_weight(k.ps.mode, k.sTa, k.sTb, tp, length);
+	if (rot_n == 0 || k.pr.mode == kClipCopy) {
+		out.rot = q4(k.rVa.x, k.rVa.y, k.rVa.z, k.rVa.w);
 	} else {
 		// Quaternion::slerp, not renormalised; a wave none of whose lanes gets here skips it
-		const Q r = blend_slerp(q4(rVa.x, rVa.y, rVa.z, rVa.w), q4(rVb.x, rVb.y, rVb.z, rVb.w), rc, lv);
+		const Q r = blend_slerp(q4(k.rVa.x, k.rVa.y, k.rVa.z, k.rVa.w), q4(k.rVb.x, k.rVb.y, k.rVb.z, k.rVb.w), rc, lv);
 		out.rot = q4(blend_canon(r.x), blend_canon(r.y), blend_canon(r.z), blend_canon(r.w));
 	}
-	out.pos = clip_value_vec(pp, pc, pVa, pVb);
-	out.scl = clip_value_vec(ps, sc, sVa, sVb);
+	out.pos = clip_value_vec(k.pp, pc, k.pVa, k.pVb);
+	out.scl = clip_value_vec(k.ps, sc, k.sVa, k.sVb);
+}
+// hp / hr / hs: the bone's three headers in `info`'s clip, already loaded -- a caller that samples
+// several clips loads the next one's while this one's keys are searched.  What a lane waits for is
+// memory, so the loads are arranged in as few dependent rounds as the data allows: the search
+// steps, three loads each; then the two key times and the two key values of all three channels at
+// once.  clip_sample_channels_at starts from tp, a finite time step 3 has already mapped into the
+// clip (root_motion.h samples the ends of a frame's segments, the clip's end among them);
+// clip_sample_channels maps the raw time t and calls it.
+GDI ClipSampled clip_sample_channels_at(const ClipView &v, const ClipInfo &info, const ClipHeader &hp, const ClipHeader &hr,
+		const ClipHeader &hs, double tp, int lv) {
+	ClipChan pos = clip_chan(v, hp), rot = clip_chan(v, hr), scl = clip_chan(v, hs);
+	ClipSampled out;
+	out.has_pos = pos.n != 0, out.has_rot = rot.n != 0, out.has_scl = scl.n != 0;
+	clip_search(pos, rot, scl, tp);
+	clip_eval(clip_load(pos, rot, scl), rot.n, tp, info.length, lv, out);
 	return out;
+}
+GDI ClipSampled clip_sample_channels(const ClipView &v, const ClipInfo &info, const ClipHeader &hp, const ClipHeader &hr,
+		const ClipHeader &hs, double t, int lv) {
+	if (!clip_finite(t)) { // no key is read
+		ClipSampled out;
+		out.has_pos = hp.key_count != 0, out.has_rot = hr.key_count != 0, out.has_scl = hs.key_count != 0;
+		const float nan = clip_nan();
+		out.rot = q4(nan, nan, nan, nan), out.pos = v3(nan, nan, nan), out.scl = v3(nan, nan, nan);
+		return out;
+	}
+	return clip_sample_channels_at(v, info, hp, hr, hs, clip_time(t, info.length, info.loop_mode), lv);
 }
 
 // One bone of one skeleton: out10 = the pose (quaternion xyzw, position, scale) of `bone` at raw

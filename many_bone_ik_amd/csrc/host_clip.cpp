@@ -6,13 +6,16 @@
 // the same way (k_clip_layers.hip, clip_layers.h).  A set made by
 // mbik_clipset_create_shaped carries blend-shape tracks as well: mbik_clip_sample_shapes and
 // mbik_clip_sample_shapes_layers write the [count][P] weights the shaped skinning reads
-// (k_clip_shapes.hip, clip_shapes.h).
+// (k_clip_shapes.hip, clip_shapes.h).  mbik_clip_root_motion[_layers] extract the root
+// bone's motion over the frame from the same tables and mbik_root_motion_apply composes it into
+// skeleton_global (k_root_motion.hip, root_motion.h).
 #include "host.h"
 
 #include <cmath>
 #include <cstddef>
 
 #include "clip_shapes.h"
+#include "root_motion.h"
 
 using namespace mbik_host;
 
@@ -121,6 +124,63 @@ int check_layers_call(int32_t B, int32_t count, int32_t layer_count, const mbik_
 static_assert(sizeof(mbik_clip_layer) == sizeof(mbik::ClipLayer) && offsetof(mbik_clip_layer, clip) == offsetof(mbik::ClipLayer, clip) &&
 				offsetof(mbik_clip_layer, weight) == offsetof(mbik::ClipLayer, weight),
 		"mbik_clip_layer is clip_layers.h's ClipLayer");
+
+// The checks of the two root-motion extraction calls; 0 = go on, 1 = nothing to do.  `layers` null: the plain form, whose
+// `time` takes the records' place.
+int check_root_call(int32_t B, int32_t clip_count, int32_t count, int32_t layer_count, int32_t root_bone, bool plain,
+		const mbik_clip_layer *layers, const double *time_prev, const double *time, const int32_t *clip_index, int32_t clip, uint32_t flags,
+		const float *motion_out, const float *pose) {
+	if (count < 0) return fail(MBIK_EINVAL, "negative count");
+	if (root_bone < 0 || root_bone >= B)
+		return fail(MBIK_EINVAL, "root_bone " + std::to_string(root_bone) + " outside [0, " + std::to_string(B) + ")");
+	if (layer_count < 1 || layer_count > MBIK_CLIP_MAX_LAYERS)
+		return fail(MBIK_EINVAL, "layer_count " + std::to_string(layer_count) + " outside [1, " + std::to_string(MBIK_CLIP_MAX_LAYERS) + "]");
+	if (flags & ~MBIK_CLIP_LAYERS_NORMALIZE) return fail(MBIK_EINVAL, "unknown flags " + std::to_string(flags));
+	if (plain && !clip_index && (clip < 0 || clip >= clip_count))
+		return fail(MBIK_EINVAL, "clip " + std::to_string(clip) + " outside the set's " + std::to_string(clip_count) + " clips");
+	if (count == 0) return 1;
+	if (!plain && !layers) return fail(MBIK_EINVAL, "null layers");
+	if (plain && !time) return fail(MBIK_EINVAL, "null time");
+	if (!time_prev) return fail(MBIK_EINVAL, "null time_prev");
+	if (!motion_out) return fail(MBIK_EINVAL, "null motion_out");
+	if (!plain && reinterpret_cast<uintptr_t>(layers) % 8) return fail(MBIK_EINVAL, "layers is not 8-byte aligned");
+	if (plain && reinterpret_cast<uintptr_t>(time) % 8) return fail(MBIK_EINVAL, "time is not 8-byte aligned");
+	if (reinterpret_cast<uintptr_t>(time_prev) % 8) return fail(MBIK_EINVAL, "time_prev is not 8-byte aligned");
+	const size_t per = (size_t)count * layer_count, out_bytes = (size_t)count * 10 * sizeof(float);
+	if (!plain && overlap(layers, per * sizeof(mbik_clip_layer), motion_out, out_bytes)) return fail(MBIK_EINVAL, "motion_out overlaps layers");
+	if (plain && overlap(time, per * sizeof(double), motion_out, out_bytes)) return fail(MBIK_EINVAL, "motion_out overlaps time");
+	if (overlap(time_prev, per * sizeof(double), motion_out, out_bytes)) return fail(MBIK_EINVAL, "motion_out overlaps time_prev");
+	if (plain && clip_index && overlap(clip_index, (size_t)count * sizeof(int32_t), motion_out, out_bytes))
+		return fail(MBIK_EINVAL, "motion_out overlaps clip_index");
+	if (pose && overlap(pose, (size_t)count * B * 10 * sizeof(float), motion_out, out_bytes)) return fail(MBIK_EINVAL, "motion_out overlaps pose");
+	return 0;
+}
+
+int check_root_apply(int32_t count, const float *motion, uint32_t flags, const float *skeleton_global) {
+	if (count < 0) return fail(MBIK_EINVAL, "negative count");
+	if (flags & ~MBIK_ROOT_MOTION_ORTHONORMALIZE) return fail(MBIK_EINVAL, "unknown flags " + std::to_string(flags));
+	if (count == 0) return 1;
+	if (!motion) return fail(MBIK_EINVAL, "null motion");
+	if (!skeleton_global) return fail(MBIK_EINVAL, "null skeleton_global");
+	if (overlap(motion, (size_t)count * 10 * sizeof(float), skeleton_global, (size_t)count * 12 * sizeof(float)))
+		return fail(MBIK_EINVAL, "skeleton_global overlaps motion");
+	return 0;
+}
+static_assert(MBIK_ROOT_MOTION_ORTHONORMALIZE == mbik::kRootMotionOrthonormalize, "the flag is root_motion.h's");
+
+// The host form of both extraction calls: one skeleton after the other through root_motion.h.
+void root_motion_host(const mbik::ClipView &v, int32_t libm, int32_t count, int32_t K, int32_t root, const mbik::ClipLayer *L,
+		const double *time_prev, const double *time, const int32_t *clip_index, int32_t clip, uint32_t flags, float *motion_out, float *pose) {
+	for (int64_t s = 0; s < count; s++) {
+		float *pose_s = pose ? pose + s * v.B * 10 : nullptr;
+		if (L) {
+			mbik::root_motion_skeleton(v, mbik::RootLayers{L + s * K, time_prev + s * K}, K, flags, root, libm, motion_out + s * 10, pose_s);
+		} else {
+			const mbik::RootPlain src{mbik::ClipLayer{time[s], clip_index ? clip_index[s] : clip, 1.0f}, time_prev[s]};
+			mbik::root_motion_skeleton(v, src, 1, 0u, root, libm, motion_out + s * 10, pose_s);
+		}
+	}
+}
 
 size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
@@ -393,6 +453,72 @@ int32_t mbik_clip_sample_shapes_layers_cpu(int32_t bone_count, const float *rest
 	const mbik::ClipLayer *L = reinterpret_cast<const mbik::ClipLayer *>(layers);
 	for (int64_t s = 0; s < count; s++)
 		for (int32_t j = 0; j < v.P; j++) weights_out[s * v.P + j] = mbik::shape_layers(v, L + s * layer_count, layer_count, flags, j);
+	return MBIK_OK;
+}
+
+int32_t mbik_clip_root_motion(mbik_clipset *s, int32_t count, int32_t root_bone, const double *time_prev, const double *time,
+		const int32_t *clip_index, int32_t clip, float *motion_out, float *pose, void *hip_stream) {
+	if (!s) return fail(MBIK_EINVAL, "null clip set");
+	const int rc = check_root_call(s->B, s->clip_count, count, 1, root_bone, true, nullptr, time_prev, time, clip_index, clip, 0u, motion_out, pose);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	DeviceGuard guard(s->device);
+	hipError_t e = mbik::launch_root_motion(reinterpret_cast<hipStream_t>(hip_stream), s->view, s->libm, count, 1, root_bone, nullptr, time_prev,
+			time, clip_index, clip, 0u, motion_out, pose);
+	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("root motion launch failed: ") + hipGetErrorString(e));
+	return MBIK_OK;
+}
+
+int32_t mbik_clip_root_motion_layers(mbik_clipset *s, int32_t count, int32_t layer_count, int32_t root_bone, const mbik_clip_layer *layers,
+		const double *time_prev, uint32_t flags, float *motion_out, float *pose, void *hip_stream) {
+	if (!s) return fail(MBIK_EINVAL, "null clip set");
+	const int rc = check_root_call(s->B, s->clip_count, count, layer_count, root_bone, false, layers, time_prev, nullptr, nullptr, 0, flags,
+			motion_out, pose);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	DeviceGuard guard(s->device);
+	hipError_t e = mbik::launch_root_motion(reinterpret_cast<hipStream_t>(hip_stream), s->view, s->libm, count, layer_count, root_bone,
+			reinterpret_cast<const mbik::ClipLayer *>(layers), time_prev, nullptr, nullptr, 0, flags, motion_out, pose);
+	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("layered root motion launch failed: ") + hipGetErrorString(e));
+	return MBIK_OK;
+}
+
+int32_t mbik_root_motion_apply(mbik_clipset *s, int32_t count, const float *motion, uint32_t flags, float *skeleton_global, void *hip_stream) {
+	if (!s) return fail(MBIK_EINVAL, "null clip set");
+	const int rc = check_root_apply(count, motion, flags, skeleton_global);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	DeviceGuard guard(s->device);
+	hipError_t e = mbik::launch_root_apply(reinterpret_cast<hipStream_t>(hip_stream), count, motion, flags, skeleton_global);
+	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("root motion apply launch failed: ") + hipGetErrorString(e));
+	return MBIK_OK;
+}
+
+int32_t mbik_clip_root_motion_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		int32_t libm_variant, int32_t count, int32_t root_bone, const double *time_prev, const double *time, const int32_t *clip_index,
+		int32_t clip, float *motion_out, float *pose) {
+	Packed pk;
+	if (int rc = pack(bone_count, rest_pose, clip_count, clips, libm_variant, pk)) return rc;
+	const int rc = check_root_call(bone_count, clip_count, count, 1, root_bone, true, nullptr, time_prev, time, clip_index, clip, 0u, motion_out, pose);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	root_motion_host(pk.view(bone_count), libm_variant, count, 1, root_bone, nullptr, time_prev, time, clip_index, clip, 0u, motion_out, pose);
+	return MBIK_OK;
+}
+
+int32_t mbik_clip_root_motion_layers_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
+		int32_t libm_variant, int32_t count, int32_t layer_count, int32_t root_bone, const mbik_clip_layer *layers, const double *time_prev,
+		uint32_t flags, float *motion_out, float *pose) {
+	Packed pk;
+	if (int rc = pack(bone_count, rest_pose, clip_count, clips, libm_variant, pk)) return rc;
+	const int rc = check_root_call(bone_count, clip_count, count, layer_count, root_bone, false, layers, time_prev, nullptr, nullptr, 0, flags,
+			motion_out, pose);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	root_motion_host(pk.view(bone_count), libm_variant, count, layer_count, root_bone, reinterpret_cast<const mbik::ClipLayer *>(layers),
+			time_prev, nullptr, nullptr, 0, flags, motion_out, pose);
+	return MBIK_OK;
+}
+
+int32_t mbik_root_motion_apply_cpu(int32_t count, const float *motion, uint32_t flags, float *skeleton_global) {
+	const int rc = check_root_apply(count, motion, flags, skeleton_global);
+	if (rc) return rc < 0 ? rc : MBIK_OK;
+	for (int64_t s = 0; s < count; s++) mbik::root_motion_apply(motion + s * 10, flags, skeleton_global + s * 12);
 	return MBIK_OK;
 }
 

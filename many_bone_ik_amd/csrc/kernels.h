@@ -231,6 +231,15 @@ hipError_t launch_clip_shapes(hipStream_t st, const ShapeView &v, int64_t total_
 		int clip, float *weights_out);
 hipError_t launch_clip_shapes_layers(hipStream_t st, const ShapeView &v, int64_t total_weights, const ClipLayer *layers, int layer_count,
 		uint32_t flags, float *weights_out);
+// k_root_motion.hip: mbik_clip_root_motion[_layers] and mbik_root_motion_apply (root_motion.h).  The plain form and a call
+// with one layer: one thread per skeleton, 64 skeletons a block, 2.5 KiB of static LDS; 2 to 8 layers: a lane per (skeleton,
+// layer), 64 / layer_count skeletons a block, 8.25 KiB.  layers non-null: [count][layer_count] records and time_prev
+// [count][layer_count]; layers null: the plain form, time / time_prev [count] and clip_index or clip.  pose ([count][v.B][10])
+// may be null.  The kernels test every clip index themselves.  The apply kernel works on skeleton_global [count][12] in
+// place, no LDS.
+hipError_t launch_root_motion(hipStream_t st, const ClipView &v, int libm, int count, int layer_count, int root, const ClipLayer *layers,
+		const double *time_prev, const double *time, const int32_t *clip_index, int clip, uint32_t flags, float *motion_out, float *pose);
+hipError_t launch_root_apply(hipStream_t st, int count, const float *motion, uint32_t flags, float *skeleton_global);
 #ifdef MBIK_PROF
 // Diagnostic cycle accounting (-DMBIK_PROF): each kernel TU has its own counters; adds them to
 // out[24] and clears them.
