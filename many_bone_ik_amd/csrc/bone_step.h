@@ -330,13 +330,31 @@ template <int CLS>
 struct StepFix {
 	static constexpr int cls = CLS;
 };
+// StepRoot: the step of a SCHED_ROOT4 row (plan.h) -- one translating root bone without limits or
+// pin, four effectors with the default priorities built by the group's four lanes into the staged
+// area.  The lane count, the effector and heading counts and the translation are compile-time
+// constants, so the staged branch's loops over the headings unroll (every LDS read of a sum issues
+// before the first add instead of four headings a round trip) and the swing, twist and pin code
+// is gone.  The arithmetic is the same text.
+struct StepRoot {
+	static constexpr int cls = 100;
+};
 template <bool STAB, bool PR, int TA, bool HELP, bool XS, int PM, bool SEL, bool XW, class SH = StepDyn, class LV, class GV, class FP, class IP>
 __device__ void bone_step(const DevPlan &t, int seg, int k, int j, int m, int xs, size_t s, const LV &L, const GV &G, const FP TG,
 		const FP ST, const IP SF, const FP HS, const FP OE, const FP MS, double &prev_dev, const EffPre &pre, bool hoist,
 		const float4 *hrec, int *hfl, int hseq, bool *hstuck, const float *xw MBIK_PROF_PARAM) {
-	constexpr bool FIX = SH::cls != 0;
+	constexpr bool ROOT = SH::cls == StepRoot::cls;
+	constexpr bool FIX = SH::cls != 0 && !ROOT;
 	static_assert(!FIX || (!STAB && !XS && !XW), "step classes: the one-wave builds without stabilization");
-	constexpr mbik::StepClassShape shape = mbik::step_class_shape(SH::cls);
+	static_assert(!ROOT || (!STAB && !XS && !XW && PM == mbik::kPrioDefault), "root rows: the one-wave default-priority builds");
+	constexpr mbik::StepClassShape shape = mbik::step_class_shape(FIX ? SH::cls : 0);
+	if constexpr (ROOT) {
+		// four effectors, one per lane of the group, staged
+		m = mbik::kRootLanes;
+		xs = 0;
+		hoist = false;
+		__builtin_assume(j >= 0 && j < mbik::kRootLanes);
+	}
 	if constexpr (FIX) {
 		// one hoisted effector solved by one lane: the segment's heading path
 		m = 1;
@@ -352,7 +370,8 @@ __device__ void bone_step(const DevPlan &t, int seg, int k, int j, int m, int xs
 	const int4 sr = t.step_rec[k];
 	const int b = sr.x & 0xffff;
 	// bone_flags | SR_* bits (a class fixes its kStepClassFlags)
-	const int flags = FIX ? ((sr.z & 0xffff & ~mbik::kStepClassFlags) | shape.flags) : (sr.z & 0xffff);
+	const int flags = FIX ? ((sr.z & 0xffff & ~mbik::kStepClassFlags) | shape.flags)
+			: ROOT ? (sr.z & 0xffff & ~(mbik::BF_ORIENT | mbik::BF_AXIAL | mbik::BF_PINNED | mbik::SR_PARENT_GLOBAL)) : (sr.z & 0xffff);
 	const int d0 = sr.z >> 16;                 // path index of b's first descendant
 	const int slot = (sr.y >> 16) - 1;         // constraint slot
 	const bool hasP = (flags & mbik::SR_HAS_POSE_PARENT) != 0;
@@ -401,9 +420,10 @@ __device__ void bone_step(const DevPlan &t, int seg, int k, int j, int m, int xs
 		Gb = hasP ? P * Lb : Lb;
 		sto = slerp_to(Gb.b);
 	}
-	const bool translate = !FIX && (t.seg_flags[seg] & mbik::SF_TRANSLATE) != 0;
-	const int e0 = t.seg_eff_off[seg], e1 = FIX ? e0 + 1 : t.seg_eff_off[seg + 1];
-	const int nh = FIX ? 2 : t.seg_nh[seg]; // (a class: two or more headings, only compared below)
+	const bool translate = ROOT || (!FIX && (t.seg_flags[seg] & mbik::SF_TRANSLATE) != 0);
+	const int e0 = t.seg_eff_off[seg], e1 = FIX ? e0 + 1 : ROOT ? e0 + mbik::kRootLanes : t.seg_eff_off[seg + 1];
+	// (a class: two or more headings, only compared below)
+	const int nh = FIX ? 2 : ROOT ? mbik::kRootHeadings : t.seg_nh[seg];
 	MBIK_PROF_T(ph0);
 	MBIK_PROF_ADD(8, pt0, ph0);
 	const double *hw = t.seg_hw + t.seg_hw_off[seg];

@@ -82,7 +82,9 @@ int upload_topology(mbik_plan *p) {
 	for (size_t i = 0; i < rows.size(); i++) {
 		// .w: the SCHED_* bits, and above bit 8 the row's longest segment in bone-steps (row_steps)
 		const int nq = mbik::row_max_steps(h, (int)(i / (size_t)h.K));
-		rows[i] = make_int4(h.sched[i].seg, h.sched[i].j, h.sched[i].m, h.sched[i].flags | (nq << 8));
+		// (and SCHED_ROOT4, which only this copy carries)
+		const int root4 = mbik::row_is_root4(h, (int)(i / (size_t)h.K)) ? mbik::SCHED_ROOT4 : 0;
+		rows[i] = make_int4(h.sched[i].seg, h.sched[i].j, h.sched[i].m, h.sched[i].flags | root4 | (nq << 8));
 	}
 	// the rows' step classes follow the schedule (HostPlan::step_class; solve_block.h row_classes):
 	// no table pointer of their own, so DevPlan -- every solve kernel's argument -- keeps its size

@@ -994,6 +994,19 @@ int row_max_steps(const HostPlan &p, int row) {
 	return n;
 }
 
+bool row_is_root4(const HostPlan &p, int row) {
+	if (p.K != kRootLanes || p.wave_roles || p.stabilization_passes > 0 || p.constraint_mode) return false;
+	const SchedTask *tk = &p.sched[(size_t)row * p.K];
+	const int sg = tk[0].seg;
+	if (sg < 0) return false;
+	for (int l = 0; l < p.K; l++)
+		if (tk[l].seg != sg || tk[l].j != l || tk[l].m != p.K || tk[l].flags != 0) return false;
+	if (p.seg_bone_off[sg + 1] - p.seg_bone_off[sg] != 1 || (p.seg_flags[sg] & (SF_TRANSLATE | SF_STAB)) != SF_TRANSLATE) return false;
+	const int b = p.seg_bones[p.seg_bone_off[sg]];
+	if ((p.bone_flags[b] & (BF_ORIENT | BF_AXIAL | BF_PINNED)) || p.bone_pose_parent[b] >= 0) return false;
+	return p.seg_eff_off[sg + 1] - p.seg_eff_off[sg] == kRootLanes && p.seg_nh[sg] == kRootHeadings;
+}
+
 int64_t rw_record_bytes(const HostPlan &p) {
 	// K / 2 records, then K / 2 counters and the block's gave-up word (16-byte aligned)
 	return p.wave_roles && p.rw_xslots ? (int64_t)(p.K / 2) * kRwRecF4 * 64 * 16 + ((p.K / 2 + 1) * 4 + 15) / 16 * 16 : 0;

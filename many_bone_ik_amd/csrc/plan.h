@@ -112,6 +112,14 @@ struct SchedTask {
 // dirty chains are disjoint once it has cleaned its own, over the group's waves (cmode.h); its
 // row's tasks carry SCHED_COOP too (two block barriers per bone-step).
 constexpr int32_t SCHED_XS = 1, SCHED_CHAIN = 2, SCHED_COOP = 4, SCHED_CMSPLIT = 8;
+// SCHED_ROOT4 (device copy of the schedule only, upload_topology): the row is one translating
+// one-bone root segment without limits, pin or stabilization, its four effectors built by the four
+// lanes of the skeleton's group with staged headings, kRootHeadings of them when every effector
+// has the default priorities (row_is_root4).  The one-wave placement-0 kernels built for those
+// priorities run the row's step with that shape compiled in (bone_step.h StepRoot).  Not a step
+// class: HostPlan::step_class keeps 0 for the row.
+constexpr int32_t SCHED_ROOT4 = 16;
+constexpr int kRootLanes = 4, kRootHeadings = 5 * kRootLanes;
 
 struct HostPlan {
 	// ---- topology (shared by the batch) ----
@@ -287,6 +295,8 @@ int64_t rw_record_bytes(const HostPlan &plan);
 int64_t rw_extra_lds_bytes(const HostPlan &plan);
 // The longest segment of schedule row `row`, in bone-steps.
 int row_max_steps(const HostPlan &plan, int row);
+// Whether schedule row `row` has the shape SCHED_ROOT4 names.
+bool row_is_root4(const HostPlan &plan, int row);
 // The class of bone-step q of schedule row `row` (HostPlan::step_class); 0 = none.
 int step_class_at(const HostPlan &plan, int row, int q);
 

@@ -53,6 +53,14 @@ __device__ __forceinline__ int step_class_of(const int *rcls, int q) {
 	return __builtin_amdgcn_readfirstlane((rcls[q >> 2] >> (8 * (q & 3))) & 0xff);
 }
 
+// Whether schedule row r is a whole-plan solve's SCHED_ROOT4 row (plan.h) in a build that has the
+// shape (PM: the default priorities): wave-uniform, a scalar branch to bone_step's StepRoot.
+template <int PM>
+__device__ __forceinline__ bool row_root4(const DevPlan &t, int r, int seg_lo, int seg_hi) {
+	if constexpr (PM != mbik::kPrioDefault) return false;
+	return seg_lo == 0 && seg_hi >= t.NS - 1 && (__builtin_amdgcn_readfirstlane(t.sched[r * t.K].w) & mbik::SCHED_ROOT4) != 0;
+}
+
 // RW (wave roles, HostPlan::wave_roles): the block is RW waves; lane = skeleton (64 per block),
 // wave = the schedule's role, so every topology value a wave reads is uniform over it.
 template <bool STAB, int PL, bool HOIST = true, bool T32 = true, bool HELP = false, bool XS = false, int PM = 0, int RW = 0>
@@ -256,6 +264,7 @@ __device__ __forceinline__ void solve_block(DevPlan &t, int blk, int first, int 
 				const bool hoist = act && t.seg_eff_off[seg + 1] - e0 == 1 && (task.z == 1 || t.seg_nh[seg] == 1);
 				if (hoist) load_eff<kTab32>(t, t.seg_effs[e0], TG, s, t.seg_hw + t.seg_hw_off[seg] + t.seg_eff_hoff[e0], pre);
 				const int *rcls = row_classes(t, r);
+				const bool root4 = row_root4<PM>(t, r, seg_lo, seg_hi);
 				for (int q = 0; q < nq; q++, seq++) {
 					MBIK_PROF_T(hw0);
 					bool b_ready;
@@ -275,7 +284,14 @@ __device__ __forceinline__ void solve_block(DevPlan &t, int blk, int first, int 
 									task.w & mbik::SCHED_XS, s, L, G, TG, ST, SF, HS, OE, MS, prev_dev, pre, hoist, hrec, b_ready ? nullptr : hfl, seq,
 									&stuck, nullptr MBIK_PROF_ARG);
 					};
-					switch (step_class_of(rcls, q)) {
+					bool stepped = false;
+					if constexpr (PM == mbik::kPrioDefault) {
+						if (root4) {
+							step(StepRoot{});
+							stepped = true;
+						}
+					}
+					if (!stepped) switch (step_class_of(rcls, q)) {
 					case 1: step(StepFix<1>{}); break;
 					case 2: step(StepFix<2>{}); break;
 					default: step(StepDyn{});
@@ -389,6 +405,7 @@ __device__ __forceinline__ void solve_block(DevPlan &t, int blk, int first, int 
 			// placement-0 build without stabilization; a packed level's lanes are at different steps).
 			constexpr bool kClasses = !STAB && PL == 0 && HOIST && T32 && !XS && RW == 0;
 			const int *rcls = kClasses && r1 == r + 1 ? row_classes(t, r) : nullptr;
+			const bool root4 = kClasses && r1 == r + 1 && row_root4<PM>(t, r, seg_lo, seg_hi);
 			for (int q = 0;; q++) {
 				while (k >= ke && rr + 1 < r1) {
 					task = t.sched[++rr * K + role];
@@ -413,7 +430,14 @@ __device__ __forceinline__ void solve_block(DevPlan &t, int blk, int first, int 
 								task.w & mbik::SCHED_XS, s, L, G, TG, ST, SF, HS, OE, MS, prev_dev, pre, hoist, nullptr, nullptr, 0, nullptr,
 								nullptr MBIK_PROF_ARG);
 					};
-					switch (rcls ? step_class_of(rcls, q) : 0) {
+					bool stepped = false;
+					if constexpr (PM == mbik::kPrioDefault) {
+						if (root4) {
+							step(StepRoot{});
+							stepped = true;
+						}
+					}
+					if (!stepped) switch (rcls ? step_class_of(rcls, q) : 0) {
 					case 1: step(StepFix<1>{}); break;
 					case 2: step(StepFix<2>{}); break;
 					default: step(StepDyn{});
