@@ -657,6 +657,146 @@ int32_t mbik_clip_root_motion_layers_cpu(int32_t bone_count, const float *rest_p
 		const double *time_prev, uint32_t flags, float *motion_out, float *pose);
 int32_t mbik_root_motion_apply_cpu(int32_t count, const float *motion, uint32_t flags, float *skeleton_global);
 
+/* Playback: AnimationPlayer for a crowd.  The layered calls above read layers [count][K] and
+ * time_prev [count][K]; a playback object keeps what produces them -- per skeleton the current
+ * animation's position and speed, the clips of a cross-fade that are still fading out, whether
+ * the clip has ended -- on the device, and mbik_playback_advance moves it one frame on and writes
+ * both arrays there.  A playing crowd then uploads its events only (somebody starts a new clip):
+ * a list of commands, and nothing at all on a frame without one.  It is AnimationPlayer's play()
+ * with a blend time, speed_scale, animation_set_next and set_blend_time.  Purely additive to ABI
+ * 15: new symbols and structs only, no existing struct or call changed, MBIK_ABI_VERSION stays 15.
+ * A caller detects the feature by the presence of the symbol mbik_playback_advance.
+ *
+ * A playback object owns the state of `capacity` skeletons with K = layer_count slots each, on
+ * the set's device.  It takes the clip count and each clip's length and loop_mode from the set
+ * when it is created; the set may be destroyed before the object.  A new object has every slot
+ * off.  mbik_playback_write and mbik_playback_read convert skeletons [first, first + n) from and
+ * to the public records (host memory, [n][K] slots and [n] flag words); they are synchronous, and
+ * the caller orders them against advances in flight on other streams.
+ *
+ * State of one skeleton.  Slot 0 is the current animation (its blend_left and blend_time are
+ * stored as +0).  Slots 1..K-1 are the clips fading out, oldest first and compact: an off slot
+ * (clip == -1, every other field +0) is followed only by off slots, slot 0 included.  Its flag
+ * word holds MBIK_PLAYBACK_STARTED (slot 0 was started and has not been shown yet) and
+ * MBIK_PLAYBACK_ENDED (slot 0's LOOP_NONE clip has run to its end).
+ *
+ * Semantics -- Godot's core is not part of the reference tree, so mbik_playback_advance_cpu is the
+ * specification, modelled on Godot 4.3's AnimationPlayer::play, _process_playback_data and
+ * _blend_playback_data.  The device runs the same code and gives the same bits.  Every operation
+ * is IEEE and unfused, in the order written; "time mapping" is mbik_clip_sample's step 3 (clamp
+ * into [0, L] for LOOP_NONE, fposmod for LOOP_LINEAR); L and loop_mode are those of the slot's
+ * clip; max(0, x) is (x > 0 ? x : +0).  For skeleton s < count, in this order:
+ *   A. Commands.  The list is sorted by skeleton, non-decreasing.  lo = 0, hi = cmd_count; while
+ *      lo < hi: mid = lo + (hi - lo) / 2; cmds[mid].skeleton < s ? lo = mid + 1 : hi = mid.  Then
+ *      the entries i = lo, lo + 1, ... are applied in order while i < cmd_count and
+ *      cmds[i].skeleton == s.  An unsorted list gives whatever that search gives; nothing outside
+ *      [0, cmd_count) is read, and an entry whose skeleton lies outside [0, count) is never
+ *      applied.  One command:
+ *        clip == -1: stop -- every slot off, flags 0.
+ *        clip outside [-1, clip_count), or speed not finite: ignored, event BAD_COMMAND.
+ *        otherwise play(clip, start, speed, blend_time):
+ *          bt = blend_time if blend_time >= 0; else (negative or NaN) blend_times[from][clip]
+ *          with from = slot 0's clip, when slot 0 is on and the table was given; else
+ *          default_blend_time (0 without a desc).
+ *          If slot 0 is on and bt > 0: cur = max(0, 1.0f - sum) with sum the float sum of the
+ *          fades' blend_left from +0, ascending; the fade (slot 0's clip, pos, speed, blend_left
+ *          = cur, blend_time = bt) is appended behind the last fade.  Without a free slot the
+ *          oldest fade (slot 1) is dropped first and the others move up, event FADE_DROPPED; with
+ *          K == 1 the new fade itself is dropped, with the same event.  Otherwise (slot 0 off, or
+ *          not bt > 0) every fade goes off.
+ *          Slot 0 becomes (clip, start', speed, +0, +0) and flags become STARTED.  start' is the
+ *          time mapping of a finite start; of any other start, L when speed's sign bit is set,
+ *          else +0.0.
+ *   B. Advance.  g = (double)speed_scale * delta.  An on slot has step = g * (double)speed and
+ *      prev = pos.  "pos advances" means n = pos + step and, if n is finite, pos = the time
+ *      mapping of n (else pos stays).
+ *      Slot 0, when on: with STARTED the bit is cleared, event STARTED, pos stays -- the first
+ *      frame of a clip shows its start, as Godot's p_started does.  Else with ENDED pos stays.
+ *      Else pos advances; then for LOOP_NONE, (step > 0 && n >= L) || (step < 0 && n <= 0) sets
+ *      ENDED, raises event ENDED and takes every fade off (AnimationPlayer clears its blend list
+ *      at end_reached); for LOOP_LINEAR, pos != n raises event LOOPED.
+ *      Each fade j >= 1 that is still on: pos advances (no flags, no events), and blend_left =
+ *      blend_left - (float)(fabs(g) / (double)blend_time).  A fade with !(blend_left > 0) goes
+ *      off.  Then the fades are compacted, stably.
+ *   C. Output.  layers_out[s][j] = (pos_j, clip_j, w_j) and time_prev_out[s][j] = prev_j, with
+ *      w_j = blend_left_j for a fade and w_0 = max(0, 1.0f - sum) over the fades that are left,
+ *      summed as in A.  An off slot writes (+0.0, -1, +0.0f) and +0.0.  These are the records
+ *      mbik_clip_sample_layers, mbik_clip_sample_shapes_layers and mbik_clip_root_motion_layers
+ *      take with MBIK_CLIP_LAYERS_NORMALIZE, AnimationPlayer's cross-fade.  Positions are already
+ *      mapped, so root motion's p0 > p1 seam test works on them.  A skeleton whose slot 0 is off
+ *      has every layer off and samples to the rest pose.
+ *   D. Transition.  If ENDED was set in this advance and next was given and next[slot 0's clip]
+ *      >= 0: A's play(next, a NaN start, slot 0's speed, blend_time -1), event TRANSITIONED.  The
+ *      next advance shows the new clip's start with time_prev == time; the clip that ended fades
+ *      out from its end.
+ *      events_out[s], when given, holds the events of A to D: STARTED, ENDED, LOOPED,
+ *      TRANSITIONED, BAD_COMMAND, FADE_DROPPED.
+ * Deviations from Godot: exact compares where Godot uses is_equal_approx / is_zero_approx; a fade
+ * that has run down is removed at once (Godot keeps it one more frame at CMP_EPSILON); at most
+ * K - 1 fades; no ping-pong; a command always restarts its clip, also the one that is playing; no
+ * method, audio or signal side effects.  Backward playback (a negative speed or speed_scale)
+ * advances and samples correctly; mbik_clip_root_motion* remain forward-only.  A command's
+ * infinite blend_time is taken as it is: that fade never runs down, and mbik_playback_write
+ * refuses such a record.
+ *
+ * MBIK_EINVAL: a null object, set, out or required buffer (events_out may be NULL; cmds may be
+ * NULL when cmd_count is 0); capacity < 0; count outside [0, capacity]; layer_count outside
+ * [1, MBIK_CLIP_MAX_LAYERS]; a desc whose struct_size is too small, with a next entry outside
+ * [-1, clip_count), or with a blend time (default_blend_time included) that is not finite or
+ * negative; delta or speed_scale not finite; cmd_count < 0; when count > 0, layers_out,
+ * time_prev_out or cmds not 8-byte aligned, or outputs overlapping each other or cmds.  In
+ * mbik_playback_write (and for the state given to the _cpu entry): a range outside the capacity;
+ * unknown flag bits; a clip outside [-1, clip_count); on an on slot a pos that is not finite or
+ * outside [0, L], or a speed that is not finite; an on fade without a finite blend_time > 0 and a
+ * finite blend_left; an on slot behind an off slot.  write stores slot 0's fade fields and every
+ * field of an off slot as +0.  count == 0 returns MBIK_OK without a launch.  Device buffers on
+ * the set's device, asynchronous on hip_stream; the commands are read by the kernel only, which
+ * tests every field before it uses it; events_out needs no alignment. */
+typedef struct mbik_playback_slot {
+	double pos;              /* seconds into the clip, in [0, length] */
+	int32_t clip;            /* [0, clip_count), or -1: the slot is off */
+	float speed;             /* the slot's own speed; negative plays backward */
+	float blend_left;        /* a fade's weight; runs down to 0 over blend_time */
+	float blend_time;        /* seconds */
+} mbik_playback_slot;        /* 24 bytes */
+typedef struct mbik_playback_cmd {
+	double start;            /* seconds; not finite: the clip's start (its end for a speed with the sign bit set) */
+	int32_t skeleton;
+	int32_t clip;            /* [0, clip_count): play; -1: stop */
+	float blend_time;        /* seconds; negative or NaN: the desc's */
+	float speed;
+} mbik_playback_cmd;         /* 24 bytes */
+typedef struct mbik_playback_desc {
+	int32_t struct_size;     /* sizeof(mbik_playback_desc) */
+	float default_blend_time;
+	const int32_t *next;     /* [clip_count], -1 none (animation_set_next); or NULL */
+	const float *blend_times; /* [clip_count][clip_count] from, to (set_blend_time); or NULL */
+} mbik_playback_desc;
+typedef struct mbik_playback mbik_playback;
+#define MBIK_PLAYBACK_STARTED 1u      /* flag and event */
+#define MBIK_PLAYBACK_ENDED 2u        /* flag and event */
+#define MBIK_PLAYBACK_LOOPED 4u       /* events only, from here on */
+#define MBIK_PLAYBACK_TRANSITIONED 8u
+#define MBIK_PLAYBACK_BAD_COMMAND 16u
+#define MBIK_PLAYBACK_FADE_DROPPED 32u
+int32_t mbik_playback_create(mbik_clipset *set, int32_t capacity, int32_t layer_count, const mbik_playback_desc *desc /* or NULL */,
+		mbik_playback **out);
+void mbik_playback_destroy(mbik_playback *pb);
+int32_t mbik_playback_write(mbik_playback *pb, int32_t first, int32_t n, const mbik_playback_slot *slots /* host [n][K] */,
+		const uint32_t *flags /* host [n] */);
+int32_t mbik_playback_read(mbik_playback *pb, int32_t first, int32_t n, mbik_playback_slot *slots, uint32_t *flags);
+int32_t mbik_playback_advance(mbik_playback *pb, int32_t count, double delta, float speed_scale,
+		const mbik_playback_cmd *cmds /* device [cmd_count], or NULL when 0 */, int32_t cmd_count,
+		mbik_clip_layer *layers_out /* device [count][K] */, double *time_prev_out /* device [count][K] */,
+		uint8_t *events_out /* device [count], or NULL */, void *hip_stream);
+/* Host-only (no device needed): the same arithmetic from the same code on host buffers, with the
+ * checks above; of a clip only length and loop_mode are looked at.  slots and flags are the state,
+ * changed in place. */
+int32_t mbik_playback_advance_cpu(int32_t clip_count, const mbik_clip_desc *clips, const mbik_playback_desc *desc /* or NULL */,
+		int32_t count, int32_t layer_count, mbik_playback_slot *slots /* [count][K] */, uint32_t *flags /* [count] */, double delta,
+		float speed_scale, const mbik_playback_cmd *cmds, int32_t cmd_count, mbik_clip_layer *layers_out, double *time_prev_out,
+		uint8_t *events_out);
+
 /* Blend-shape tracks of a clip set: the [count][shape_count] weights mbik_skin_vertices_shaped and
  * mbik_skin_vertices_call read, written on the device from the times, clip indices and layer
  * records that already drive the bones.  In Godot the same Animation resource carries

@@ -38,7 +38,8 @@ EXPORTED_SYMBOLS = (
     "mbik_multi_skeletons", "mbik_multi_destroy", "mbik_capture_targets", "mbik_pose_globals", "mbik_pose_globals_cpu", "mbik_pose_blend", "mbik_pose_blend_cpu", "mbik_clipset_create", "mbik_clipset_destroy", "mbik_clip_sample", "mbik_clip_sample_cpu", "mbik_clip_sample_layers", "mbik_clip_sample_layers_cpu",
     "mbik_clipset_create_shaped", "mbik_clip_sample_shapes", "mbik_clip_sample_shapes_layers", "mbik_clip_sample_shapes_cpu",
     "mbik_clip_sample_shapes_layers_cpu", "mbik_clip_root_motion", "mbik_clip_root_motion_layers", "mbik_root_motion_apply",
-    "mbik_clip_root_motion_cpu", "mbik_clip_root_motion_layers_cpu", "mbik_root_motion_apply_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
+    "mbik_clip_root_motion_cpu", "mbik_clip_root_motion_layers_cpu", "mbik_root_motion_apply_cpu", "mbik_playback_create",
+    "mbik_playback_destroy", "mbik_playback_write", "mbik_playback_read", "mbik_playback_advance", "mbik_playback_advance_cpu", "mbik_mesh_create", "mbik_mesh_destroy",
     "mbik_skin_vertices", "mbik_skin_vertices_cpu", "mbik_mesh_launch_shape", "mbik_mesh_create_shaped", "mbik_skin_vertices_shaped",
     "mbik_skin_vertices_shaped_cpu", "mbik_mesh_bone_boxes", "mbik_bone_boxes_cpu", "mbik_skin_bounds", "mbik_skin_bounds_cpu",
     "mbik_cull_boxes", "mbik_cull_boxes_cpu", "mbik_cull_lod", "mbik_cull_lod_cpu", "mbik_skin_vertices_listed", "mbik_skin_vertices_listed_cpu",
@@ -104,6 +105,22 @@ class MbikClipLayer(C.Structure):
 CLIP_MAX_LAYERS = 8
 CLIP_LAYERS_NORMALIZE = 1
 ROOT_MOTION_ORTHONORMALIZE = 1  # MBIK_ROOT_MOTION_ORTHONORMALIZE
+
+
+class MbikPlaybackSlot(C.Structure):
+    _fields_ = [("pos", C.c_double), ("clip", C.c_int32), ("speed", C.c_float), ("blend_left", C.c_float), ("blend_time", C.c_float)]
+
+
+class MbikPlaybackCmd(C.Structure):
+    _fields_ = [("start", C.c_double), ("skeleton", C.c_int32), ("clip", C.c_int32), ("blend_time", C.c_float), ("speed", C.c_float)]
+
+
+class MbikPlaybackDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("default_blend_time", C.c_float), ("next", C.c_void_p), ("blend_times", C.c_void_p)]
+
+
+# mbik_playback: a skeleton's flag bits (the first two) and the event bits of an advance
+PLAYBACK_STARTED, PLAYBACK_ENDED, PLAYBACK_LOOPED, PLAYBACK_TRANSITIONED, PLAYBACK_BAD_COMMAND, PLAYBACK_FADE_DROPPED = 1, 2, 4, 8, 16, 32
 
 
 class MbikShapeTrack(C.Structure):
@@ -329,6 +346,19 @@ def load():
     L.mbik_clip_root_motion_layers_cpu.restype = C.c_int32
     L.mbik_root_motion_apply_cpu.argtypes = [C.c_int32, vp, C.c_uint32, vp]
     L.mbik_root_motion_apply_cpu.restype = C.c_int32
+    L.mbik_playback_create.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(MbikPlaybackDesc), C.POINTER(vp)]
+    L.mbik_playback_create.restype = C.c_int32
+    L.mbik_playback_destroy.argtypes = [vp]
+    L.mbik_playback_destroy.restype = None
+    L.mbik_playback_write.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
+    L.mbik_playback_write.restype = C.c_int32
+    L.mbik_playback_read.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
+    L.mbik_playback_read.restype = C.c_int32
+    L.mbik_playback_advance.argtypes = [vp, C.c_int32, C.c_double, C.c_float, vp, C.c_int32, vp, vp, vp, vp]
+    L.mbik_playback_advance.restype = C.c_int32
+    L.mbik_playback_advance_cpu.argtypes = [C.c_int32, C.POINTER(MbikClipDesc), C.POINTER(MbikPlaybackDesc), C.c_int32, C.c_int32, vp, vp,
+                                            C.c_double, C.c_float, vp, C.c_int32, vp, vp, vp]
+    L.mbik_playback_advance_cpu.restype = C.c_int32
     L.mbik_mesh_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.POINTER(vp)]
     L.mbik_mesh_create.restype = C.c_int32
     L.mbik_mesh_destroy.argtypes = [vp]

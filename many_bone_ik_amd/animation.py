@@ -26,6 +26,13 @@ the loop seam handled) per skeleton and hold the root bone at rest in the sample
 `ClipSet.apply_root_motion()` composes the records into skeleton_global [count][12] in place.
 `clip_root_motion_cpu()`, `clip_root_motion_layers_cpu()` and `root_motion_apply_cpu()` are the host
 forms, `synthetic_walk_clips()` the seeded generator of clips whose root bone walks and turns.
+
+Playback: `Playback` owns one `mbik_playback`, the per-skeleton playback state of a
+crowd on a `ClipSet`'s device -- AnimationPlayer's current animation, cross-fades and
+animation_set_next.  `Playback.advance()` moves it one frame on and writes the layer records and
+previous times `sample_layers()` and `root_motion_layers()` read, from a device array of commands
+(`pack_commands()`, CMD_DTYPE) or none; `Playback.write()` / `read()` exchange state (SLOT_DTYPE
+records and flag words) with the host.  `playback_advance_cpu()` is the host form.
 """
 from __future__ import annotations
 
@@ -47,6 +54,13 @@ MAX_LAYERS = _lib.CLIP_MAX_LAYERS
 LAYERS_NORMALIZE = _lib.CLIP_LAYERS_NORMALIZE
 LAYER_OFF = -1
 ROOT_MOTION_ORTHONORMALIZE = _lib.ROOT_MOTION_ORTHONORMALIZE
+# mbik_playback_slot and mbik_playback_cmd, 24 bytes each
+SLOT_DTYPE = np.dtype([("pos", "<f8"), ("clip", "<i4"), ("speed", "<f4"), ("blend_left", "<f4"), ("blend_time", "<f4")])
+CMD_DTYPE = np.dtype([("start", "<f8"), ("skeleton", "<i4"), ("clip", "<i4"), ("blend_time", "<f4"), ("speed", "<f4")])
+# a skeleton's flag bits (the first two) and the event bits of an advance
+PLAYBACK_STARTED, PLAYBACK_ENDED, PLAYBACK_LOOPED = _lib.PLAYBACK_STARTED, _lib.PLAYBACK_ENDED, _lib.PLAYBACK_LOOPED
+PLAYBACK_TRANSITIONED, PLAYBACK_BAD_COMMAND, PLAYBACK_FADE_DROPPED = _lib.PLAYBACK_TRANSITIONED, _lib.PLAYBACK_BAD_COMMAND, _lib.PLAYBACK_FADE_DROPPED
+PLAYBACK_STOP = -1  # a command's clip that stops its skeleton
 
 
 def _ptr(a):
@@ -304,6 +318,118 @@ def root_motion_apply_cpu(motion, skeleton_global, flags: int = 0):
     assert g.shape[0] == m.shape[0], (g.shape, m.shape)
     check(L.mbik_root_motion_apply_cpu(m.shape[0], _ptr(m), flags, _ptr(g)))
     return g
+
+
+def _playback_desc(clip_count, next, blend_times, default_blend_time):
+    """(mbik_playback_desc or None, the objects its pointers refer to)."""
+    if next is None and blend_times is None and default_blend_time == 0.0:
+        return None, []
+    nx = None if next is None else np.ascontiguousarray(next, np.int32).reshape(-1)
+    bt = None if blend_times is None else np.ascontiguousarray(blend_times, np.float32)
+    assert nx is None or nx.shape == (clip_count,), nx.shape
+    assert bt is None or bt.shape == (clip_count, clip_count), bt.shape
+    d = _lib.MbikPlaybackDesc()
+    d.struct_size, d.default_blend_time = C.sizeof(_lib.MbikPlaybackDesc), float(default_blend_time)
+    d.next = None if nx is None else nx.ctypes.data
+    d.blend_times = None if bt is None else bt.ctypes.data
+    return d, [nx, bt]
+
+
+def empty_state(count: int, layer_count: int):
+    """(slots [count][K] of SLOT_DTYPE, flags [count] uint32) with every slot off: a new object's state."""
+    slots = np.zeros((count, layer_count), SLOT_DTYPE)
+    slots["clip"] = LAYER_OFF
+    return slots, np.zeros(count, np.uint32)
+
+
+class Playback:
+    """The playback state of `capacity` skeletons with `layer_count` slots each on `clipset`'s GPU
+    (mbik_playback_create).  `next` [clips] (-1: none) is animation_set_next, `blend_times`
+    [clips][clips] (from, to) set_blend_time.  The set may be closed before the object."""
+
+    def __init__(self, clipset: ClipSet, capacity: int, layer_count: int, next=None, blend_times=None, default_blend_time: float = 0.0):
+        self._L = _lib.load()
+        self.capacity, self.layer_count, self.clip_count = int(capacity), int(layer_count), clipset.clip_count
+        desc, keep = _playback_desc(clipset.clip_count, next, blend_times, default_blend_time)
+        h = C.c_void_p()
+        check(self._L.mbik_playback_create(clipset.h, self.capacity, self.layer_count, None if desc is None else C.byref(desc), C.byref(h)))
+        del keep
+        self.h = h
+
+    def advance(self, delta: float, layers_ptr: int, time_prev_ptr: int, count: int, speed_scale: float = 1.0, cmds_ptr: int = 0,
+                cmd_count: int = 0, events_ptr: int = 0, stream: int = 0) -> None:
+        """mbik_playback_advance: the first `count` skeletons one frame of `delta` seconds on, after
+        the `cmd_count` commands of the device array cmds (CMD_DTYPE, sorted by skeleton); writes the
+        device arrays layers [count][K] (LAYER_DTYPE), time_prev [count][K] (float64) and, when
+        given, events [count] (uint8).  Asynchronous on `stream`."""
+        check(self._L.mbik_playback_advance(self.h, count, delta, speed_scale, C.c_void_p(cmds_ptr or None), cmd_count,
+                                            C.c_void_p(layers_ptr or None), C.c_void_p(time_prev_ptr or None), C.c_void_p(events_ptr or None),
+                                            C.c_void_p(stream or None)))
+
+    def read(self, first: int = 0, n: int | None = None):
+        """mbik_playback_read: (slots [n][K] of SLOT_DTYPE, flags [n] uint32) of skeletons [first, first + n)."""
+        n = self.capacity - first if n is None else n
+        slots, flags = np.empty((max(n, 0), self.layer_count), SLOT_DTYPE), np.empty(max(n, 0), np.uint32)
+        check(self._L.mbik_playback_read(self.h, first, n, _ptr(slots), _ptr(flags)))
+        return slots, flags
+
+    def write(self, slots, flags, first: int = 0) -> None:
+        """mbik_playback_write: the state of skeletons [first, first + len(flags)) from host records."""
+        f = np.ascontiguousarray(flags, np.uint32).reshape(-1)
+        rec = np.ascontiguousarray(slots, SLOT_DTYPE).reshape(f.shape[0], self.layer_count)
+        check(self._L.mbik_playback_write(self.h, first, f.shape[0], _ptr(rec), _ptr(f)))
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            self._L.mbik_playback_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pack_commands(skeleton, clip, start=np.nan, blend_time=-1.0, speed=1.0):
+    """Command records of CMD_DTYPE from arrays (or scalars) of one length, sorted by skeleton,
+    stably: commands for one skeleton keep their order.  clip == PLAYBACK_STOP stops a skeleton; a
+    start that is not finite is the clip's start; a negative blend_time is the object's."""
+    sk = np.asarray(skeleton, np.int32).reshape(-1)
+    out = np.empty(sk.shape, CMD_DTYPE)
+    out["skeleton"] = sk
+    out["clip"] = np.broadcast_to(np.asarray(clip, np.int32), sk.shape)
+    out["start"] = np.broadcast_to(np.asarray(start, np.float64), sk.shape)
+    out["blend_time"] = np.broadcast_to(np.asarray(blend_time, np.float32), sk.shape)
+    out["speed"] = np.broadcast_to(np.asarray(speed, np.float32), sk.shape)
+    return out[np.argsort(sk, kind="stable")]
+
+
+def playback_advance_cpu(clips, state, flags, delta: float, speed_scale: float = 1.0, cmds=None, next=None, blend_times=None,
+                         default_blend_time: float = 0.0, events: bool = True):
+    """mbik_playback_advance_cpu (host only): `state` [count][K] of SLOT_DTYPE and `flags` [count]
+    one frame on -> (state, flags, layers [count][K] of LAYER_DTYPE, time_prev [count][K], events
+    [count] uint8 or None), all new arrays.  `cmds` is used as it is given (pack_commands sorts)."""
+    L = _lib.load()
+    descs, keep = _descs([dict(length=c["length"], loop_mode=c.get("loop_mode", LOOP_NONE), tracks=[]) for c in clips])
+    desc, keep_d = _playback_desc(len(clips), next, blend_times, default_blend_time)
+    st = np.array(state, SLOT_DTYPE, order="C")
+    assert st.ndim == 2, st.shape
+    fl = np.array(flags, np.uint32, order="C").reshape(-1)
+    assert fl.shape[0] == st.shape[0], (fl.shape, st.shape)
+    cm = None if cmds is None else np.ascontiguousarray(cmds, CMD_DTYPE).reshape(-1)
+    layers, prev = np.empty(st.shape, LAYER_DTYPE), np.empty(st.shape, np.float64)
+    ev = np.empty(st.shape[0], np.uint8) if events else None
+    check(L.mbik_playback_advance_cpu(len(clips), descs, None if desc is None else C.byref(desc), st.shape[0], st.shape[1], _ptr(st), _ptr(fl),
+                                      delta, speed_scale, _ptr(cm), 0 if cm is None else cm.shape[0], _ptr(layers), _ptr(prev), _ptr(ev)))
+    del keep, keep_d
+    return st, fl, layers, prev, ev
 
 
 # the host forms of the shape calls need no rig: the pose tracks of `clips` are left out

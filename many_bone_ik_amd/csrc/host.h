@@ -28,6 +28,9 @@ using mbik::kRowTile;
 using mbik::node_area_floats;
 using mbik::node_at;
 using mbik::TopoSlice;
+namespace mbik {
+struct ClipInfo; // clip.h
+}
 
 namespace mbik_host {
 
@@ -269,6 +272,10 @@ size_t cmode_dirty_bytes(const mbik::HostPlan &h);
 size_t cmode_file_node_bytes(const mbik::HostPlan &h);
 std::vector<float> cmode_nodes_tiled(const mbik::HostPlan &h, const float *plain);
 void cmode_nodes_plain(const mbik::HostPlan &h, const float *tiled, float *plain);
+
+// What a playback object takes from a clip set at its creation (host_clip.cpp): the set's device and each clip's
+// length and loop mode, read back from the set's tables.
+int clipset_clips(const mbik_clipset *set, int &device, std::vector<mbik::ClipInfo> &clips);
 
 // plan creation (host_plan.cpp)
 int read_options(const mbik_plan_options *opts, int &libm);

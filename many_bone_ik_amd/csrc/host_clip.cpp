@@ -329,6 +329,15 @@ int create_set(int32_t bone_count, const float *rest_pose, int32_t clip_count, c
 
 } // namespace
 
+int mbik_host::clipset_clips(const mbik_clipset *set, int &device, std::vector<mbik::ClipInfo> &clips) {
+	device = set->device;
+	clips.resize((size_t)set->clip_count);
+	DeviceGuard guard(set->device);
+	if (hipMemcpy(clips.data(), set->view.clips, clips.size() * sizeof(mbik::ClipInfo), hipMemcpyDeviceToHost) != hipSuccess)
+		return fail(MBIK_EHIP, "hipMemcpy failed for the clip set's clip table");
+	return MBIK_OK;
+}
+
 extern "C" {
 
 int32_t mbik_clipset_create(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,

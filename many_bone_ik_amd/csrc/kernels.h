@@ -240,6 +240,16 @@ hipError_t launch_clip_shapes_layers(hipStream_t st, const ShapeView &v, int64_t
 hipError_t launch_root_motion(hipStream_t st, const ClipView &v, int libm, int count, int layer_count, int root, const ClipLayer *layers,
 		const double *time_prev, const double *time, const int32_t *clip_index, int clip, uint32_t flags, float *motion_out, float *pose);
 hipError_t launch_root_apply(hipStream_t st, int count, const float *motion, uint32_t flags, float *skeleton_global);
+// k_playback.hip: mbik_playback_advance (playback.h).  One thread per skeleton, 64 skeletons a block; one layer: no LDS; 2 to 8
+// layers: 12 KiB of static LDS, the block's records and previous times staged.  T's tables and `state` are the object's device
+// memory, count <= the object's capacity; cmds is device memory, [cmd_count] records of 24 bytes, 8-byte aligned, or null with
+// cmd_count 0; layers_out and time_prev_out [count][layer_count], 8-byte aligned; events_out [count] may be null.  The kernel
+// tests every command's fields itself.
+struct PlaybackTables;
+struct PlaybackState;
+struct PlaybackCmd;
+hipError_t launch_playback(hipStream_t st, const PlaybackTables &T, const PlaybackState &state, int count, int layer_count, double delta,
+		float speed_scale, const PlaybackCmd *cmds, int cmd_count, ClipLayer *layers_out, double *time_prev_out, uint8_t *events_out);
 #ifdef MBIK_PROF
 // Diagnostic cycle accounting (-DMBIK_PROF): each kernel TU has its own counters; adds them to
 // out[24] and clears them.
