@@ -67,28 +67,37 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _set_tracks(d, clip, key, record, place, floats_per_key):
+    """Fills a per-clip record's track_count / tracks from the track dicts clip[key] (`record`: their ctypes type, `place`:
+    the fields that name a track's place); the objects its pointers refer to.  A dict's "key_count", and the clip's
+    "<key>_count" (with no tracks: a null pointer), override what the arrays give: how the tests build invalid sets."""
+    tracks, count_key = clip.get(key, []), key[:-1] + "_count"
+    arr = (record * max(len(tracks), 1))()
+    keep = [arr]
+    for t, tr in zip(arr, tracks):
+        times = None if tr.get("times") is None else np.ascontiguousarray(tr["times"], np.float64).reshape(-1)
+        values = None if tr.get("values") is None else np.ascontiguousarray(tr["values"], np.float32)
+        n = tr.get("key_count", 0 if times is None else times.shape[0])
+        if values is not None and times is not None and "key_count" not in tr:
+            assert values.size == n * floats_per_key(tr), (values.shape, n)
+        keep += [times, values]
+        for f in place:
+            setattr(t, f, int(tr[f]))
+        t.interpolation, t.loop_wrap, t.key_count = int(tr.get("interpolation", LINEAR)), int(tr.get("loop_wrap", 1)), int(n)
+        t.times = None if times is None else times.ctypes.data
+        t.values = None if values is None else values.ctypes.data
+    d.track_count = int(clip.get(count_key, len(tracks)))
+    d.tracks = C.cast(arr, C.POINTER(record)) if tracks or count_key not in clip else None
+    return keep
+
+
 def _descs(clips):
     """(array of mbik_clip_desc, the objects its pointers refer to)."""
     keep = []
     descs = (_lib.MbikClipDesc * max(len(clips), 1))()
     for d, clip in zip(descs, clips):
-        tracks = clip.get("tracks", [])
-        arr = (_lib.MbikClipTrack * max(len(tracks), 1))()
-        for t, tr in zip(arr, tracks):
-            times = None if tr.get("times") is None else np.ascontiguousarray(tr["times"], np.float64).reshape(-1)
-            values = None if tr.get("values") is None else np.ascontiguousarray(tr["values"], np.float32)
-            n = tr.get("key_count", 0 if times is None else times.shape[0])
-            if values is not None and times is not None and "key_count" not in tr:
-                assert values.size == n * (4 if tr["channel"] == ROTATION else 3), (values.shape, n)
-            keep += [times, values]
-            t.bone, t.channel, t.interpolation = int(tr["bone"]), int(tr["channel"]), int(tr.get("interpolation", LINEAR))
-            t.loop_wrap, t.key_count = int(tr.get("loop_wrap", 1)), int(n)
-            t.times = None if times is None else times.ctypes.data
-            t.values = None if values is None else values.ctypes.data
-        keep.append(arr)
+        keep += _set_tracks(d, clip, "tracks", _lib.MbikClipTrack, ("bone", "channel"), lambda tr: 4 if tr["channel"] == ROTATION else 3)
         d.length, d.loop_mode = float(clip["length"]), int(clip.get("loop_mode", LOOP_NONE))
-        d.track_count = int(clip.get("track_count", len(tracks)))
-        d.tracks = C.cast(arr, C.POINTER(_lib.MbikClipTrack)) if tracks or "track_count" not in clip else None
     return descs, keep
 
 
@@ -97,22 +106,7 @@ def _shape_descs(shape_count, clips, shape_init):
     keep = []
     per_clip = (_lib.MbikClipShapeTracks * max(len(clips), 1))()
     for d, clip in zip(per_clip, clips):
-        tracks = clip.get("shape_tracks", [])
-        arr = (_lib.MbikShapeTrack * max(len(tracks), 1))()
-        for t, tr in zip(arr, tracks):
-            times = None if tr.get("times") is None else np.ascontiguousarray(tr["times"], np.float64).reshape(-1)
-            values = None if tr.get("values") is None else np.ascontiguousarray(tr["values"], np.float32).reshape(-1)
-            n = tr.get("key_count", 0 if times is None else times.shape[0])
-            if values is not None and times is not None and "key_count" not in tr:
-                assert values.size == n, (values.shape, n)
-            keep += [times, values]
-            t.shape, t.interpolation = int(tr["shape"]), int(tr.get("interpolation", LINEAR))
-            t.loop_wrap, t.key_count = int(tr.get("loop_wrap", 1)), int(n)
-            t.times = None if times is None else times.ctypes.data
-            t.values = None if values is None else values.ctypes.data
-        keep.append(arr)
-        d.track_count = int(clip.get("shape_track_count", len(tracks)))
-        d.tracks = C.cast(arr, C.POINTER(_lib.MbikShapeTrack)) if tracks or "shape_track_count" not in clip else None
+        keep += _set_tracks(d, clip, "shape_tracks", _lib.MbikShapeTrack, ("shape",), lambda tr: 1)
     init = None if shape_init is None else np.ascontiguousarray(shape_init, np.float32).reshape(-1)
     assert init is None or init.shape == (shape_count,), init.shape
     sh = _lib.MbikClipsetShapes()
@@ -129,24 +123,31 @@ def _rest(bone_count, rest_pose):
     return rest
 
 
+def _set_args(bone_count, rest_pose, clips, libm_variant, shapes=None):
+    """The arguments every entry that takes a set's description starts with -- (bone_count, rest_pose, clip_count, clips[,
+    shapes], libm_variant); shapes: (shape_count, shape_init) -- and the objects their pointers refer to."""
+    rest = _rest(bone_count, rest_pose)
+    descs, keep = _descs(clips)
+    args = [int(bone_count), _ptr(rest), len(clips), descs]
+    if shapes is not None:
+        sh, keep_sh = _shape_descs(shapes[0], clips, shapes[1])
+        args.append(C.byref(sh))
+        keep += [sh, keep_sh]
+    return args + [libm_variant], keep + [rest]
+
+
 class ClipSet:
     """Several clips of one rig on one GPU (mbik_clipset_create).  Immutable; close() frees it."""
 
     def __init__(self, bone_count: int, rest_pose, clips, libm_variant: int = 0, device: int = 0, shape_count: int = 0,
                  shape_init=None):
         self._L = _lib.load()
-        rest = _rest(bone_count, rest_pose)
-        descs, keep = _descs(clips)
         self.bone_count, self.clip_count, self.libm_variant, self.device = int(bone_count), len(clips), libm_variant, device
         self.shape_count = int(shape_count)
+        args, keep = _set_args(bone_count, rest_pose, clips, libm_variant, (self.shape_count, shape_init) if self.shape_count else None)
         h = C.c_void_p()
-        if self.shape_count == 0:
-            check(self._L.mbik_clipset_create(self.bone_count, _ptr(rest), len(clips), descs, libm_variant, device, C.byref(h)))
-        else:
-            sh, keep_sh = _shape_descs(self.shape_count, clips, shape_init)
-            check(self._L.mbik_clipset_create_shaped(self.bone_count, _ptr(rest), len(clips), descs, C.byref(sh), libm_variant, device,
-                                                     C.byref(h)))
-            del keep_sh
+        create = self._L.mbik_clipset_create_shaped if self.shape_count else self._L.mbik_clipset_create
+        check(create(*args, device, C.byref(h)))
         del keep
         self.h = h
 
@@ -224,13 +225,12 @@ def clip_sample_cpu(bone_count: int, rest_pose, clips, time, clip_index=None, cl
     """mbik_clip_sample_cpu (host only): `time` [count] seconds and `clip_index` [count] (or the one
     `clip`) -> poses [count][bones][10]."""
     L = _lib.load()
-    rest = _rest(bone_count, rest_pose)
-    descs, keep = _descs(clips)
+    args, keep = _set_args(bone_count, rest_pose, clips, libm_variant)
     t = np.ascontiguousarray(time, np.float64).reshape(-1)
     idx = None if clip_index is None else np.ascontiguousarray(clip_index, np.int32).reshape(-1)
     assert idx is None or idx.shape == t.shape, (idx.shape, t.shape)
     out = np.empty((t.shape[0], bone_count, 10), np.float32)
-    check(L.mbik_clip_sample_cpu(bone_count, _ptr(rest), len(clips), descs, libm_variant, t.shape[0], _ptr(t), _ptr(idx), clip,
+    check(L.mbik_clip_sample_cpu(*args, t.shape[0], _ptr(t), _ptr(idx), clip,
                                  _ptr(out)))
     del keep
     return out
@@ -254,13 +254,11 @@ def clip_sample_layers_cpu(bone_count: int, rest_pose, clips, layers, flags: int
     """mbik_clip_sample_layers_cpu (host only): `layers` [count][K] of LAYER_DTYPE (pack_layers) ->
     poses [count][bones][10]."""
     L = _lib.load()
-    rest = _rest(bone_count, rest_pose)
-    descs, keep = _descs(clips)
+    args, keep = _set_args(bone_count, rest_pose, clips, libm_variant)
     rec = np.ascontiguousarray(layers, LAYER_DTYPE)
     assert rec.ndim == 2, rec.shape
     out = np.empty((rec.shape[0], bone_count, 10), np.float32)
-    check(L.mbik_clip_sample_layers_cpu(bone_count, _ptr(rest), len(clips), descs, libm_variant, rec.shape[0], rec.shape[1], _ptr(rec),
-                                        flags, _ptr(out)))
+    check(L.mbik_clip_sample_layers_cpu(*args, rec.shape[0], rec.shape[1], _ptr(rec), flags, _ptr(out)))
     del keep
     return out
 
@@ -279,15 +277,14 @@ def clip_root_motion_cpu(bone_count: int, rest_pose, clips, time_prev, time, roo
     [count] (or the one `clip`) -> motion records [count][10].  `pose` (float32 [count][bones][10],
     optional) gets the rest pose's root record in place."""
     L = _lib.load()
-    rest = _rest(bone_count, rest_pose)
-    descs, keep = _descs(clips)
+    args, keep = _set_args(bone_count, rest_pose, clips, libm_variant)
     t0 = np.ascontiguousarray(time_prev, np.float64).reshape(-1)
     t1 = np.ascontiguousarray(time, np.float64).reshape(-1)
     idx = None if clip_index is None else np.ascontiguousarray(clip_index, np.int32).reshape(-1)
     assert t0.shape == t1.shape and (idx is None or idx.shape == t1.shape), (t0.shape, t1.shape)
     out = np.empty((t1.shape[0], 10), np.float32)
-    check(L.mbik_clip_root_motion_cpu(bone_count, _ptr(rest), len(clips), descs, libm_variant, t1.shape[0], root_bone, _ptr(t0), _ptr(t1),
-                                      _ptr(idx), clip, _ptr(out), _ptr(_pose_arg(pose, t1.shape[0], bone_count))))
+    check(L.mbik_clip_root_motion_cpu(*args, t1.shape[0], root_bone, _ptr(t0), _ptr(t1), _ptr(idx), clip, _ptr(out),
+                                      _ptr(_pose_arg(pose, t1.shape[0], bone_count))))
     del keep
     return out
 
@@ -297,14 +294,13 @@ def clip_root_motion_layers_cpu(bone_count: int, rest_pose, clips, layers, time_
     """mbik_clip_root_motion_layers_cpu (host only): `layers` [count][K] of LAYER_DTYPE and
     `time_prev` [count][K] seconds -> motion records [count][10]; `pose` as in clip_root_motion_cpu."""
     L = _lib.load()
-    rest = _rest(bone_count, rest_pose)
-    descs, keep = _descs(clips)
+    args, keep = _set_args(bone_count, rest_pose, clips, libm_variant)
     rec = np.ascontiguousarray(layers, LAYER_DTYPE)
     assert rec.ndim == 2, rec.shape
     t0 = np.ascontiguousarray(time_prev, np.float64).reshape(rec.shape)
     out = np.empty((rec.shape[0], 10), np.float32)
-    check(L.mbik_clip_root_motion_layers_cpu(bone_count, _ptr(rest), len(clips), descs, libm_variant, rec.shape[0], rec.shape[1], root_bone,
-                                             _ptr(rec), _ptr(t0), flags, _ptr(out), _ptr(_pose_arg(pose, rec.shape[0], bone_count))))
+    check(L.mbik_clip_root_motion_layers_cpu(*args, rec.shape[0], rec.shape[1], root_bone, _ptr(rec), _ptr(t0), flags, _ptr(out),
+                                             _ptr(_pose_arg(pose, rec.shape[0], bone_count))))
     del keep
     return out
 
@@ -445,16 +441,13 @@ def clip_sample_shapes_cpu(shape_count: int, clips, time, clip_index=None, clip:
     """mbik_clip_sample_shapes_cpu (host only): `time` [count] seconds and `clip_index` [count] (or
     the one `clip`) -> weights [count][shape_count]."""
     L = _lib.load()
-    clips = _shape_only(clips)
-    descs, keep = _descs(clips)
-    sh, keep_sh = _shape_descs(shape_count, clips, shape_init)
+    args, keep = _set_args(0, _NO_REST[:0], _shape_only(clips), 0, (shape_count, shape_init))
     t = np.ascontiguousarray(time, np.float64).reshape(-1)
     idx = None if clip_index is None else np.ascontiguousarray(clip_index, np.int32).reshape(-1)
     assert idx is None or idx.shape == t.shape, (idx.shape, t.shape)
     out = np.empty((t.shape[0], max(int(shape_count), 0)), np.float32)
-    check(L.mbik_clip_sample_shapes_cpu(0, _ptr(_NO_REST), len(clips), descs, C.byref(sh), 0, t.shape[0], _ptr(t), _ptr(idx), clip,
-                                        _ptr(out)))
-    del keep, keep_sh
+    check(L.mbik_clip_sample_shapes_cpu(*args, t.shape[0], _ptr(t), _ptr(idx), clip, _ptr(out)))
+    del keep
     return out
 
 
@@ -462,15 +455,12 @@ def clip_sample_shapes_layers_cpu(shape_count: int, clips, layers, flags: int = 
     """mbik_clip_sample_shapes_layers_cpu (host only): `layers` [count][K] of LAYER_DTYPE
     (pack_layers) -> weights [count][shape_count]."""
     L = _lib.load()
-    clips = _shape_only(clips)
-    descs, keep = _descs(clips)
-    sh, keep_sh = _shape_descs(shape_count, clips, shape_init)
+    args, keep = _set_args(0, _NO_REST[:0], _shape_only(clips), 0, (shape_count, shape_init))
     rec = np.ascontiguousarray(layers, LAYER_DTYPE)
     assert rec.ndim == 2, rec.shape
     out = np.empty((rec.shape[0], max(int(shape_count), 0)), np.float32)
-    check(L.mbik_clip_sample_shapes_layers_cpu(0, _ptr(_NO_REST), len(clips), descs, C.byref(sh), 0, rec.shape[0], rec.shape[1],
-                                               _ptr(rec), flags, _ptr(out)))
-    del keep, keep_sh
+    check(L.mbik_clip_sample_shapes_layers_cpu(*args, rec.shape[0], rec.shape[1], _ptr(rec), flags, _ptr(out)))
+    del keep
     return out
 
 

@@ -73,6 +73,13 @@ public:
 	// allocated before the old one is freed, and its contents are undefined.  Fails with
 	// MBIK_ENOMEM and the text `what`, which names what was being allocated; the old buffer stays.
 	int reserve(size_t bytes, const char *what);
+	// reserve(), then a copy of `bytes` host bytes into the buffer (synchronous): MBIK_ENOMEM "hipMalloc failed for <what>" or
+	// MBIK_EHIP "hipMemcpy failed for <what>".
+	int upload(const void *src, size_t bytes, const std::string &what) {
+		if (int rc = reserve(bytes, ("hipMalloc failed for " + what).c_str())) return rc;
+		if (hipMemcpy(p_, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(MBIK_EHIP, "hipMemcpy failed for " + what);
+		return MBIK_OK;
+	}
 	void reset();
 	size_t bytes() const { return bytes_; }
 	explicit operator bool() const { return p_ != nullptr; }
@@ -83,6 +90,36 @@ private:
 	void *p_ = nullptr;
 	size_t bytes_ = 0;
 	int device_ = 0;
+};
+
+// A table image for the device in the one format the clip set and the playback object use: sections, each from a 16-byte
+// boundary, the gaps zero, 16 spare bytes behind the last.  An empty section takes no room: it shares its offset with the
+// next one.
+class Blob {
+public:
+	// Appends a section; its offset.
+	size_t add(const void *src, size_t bytes) {
+		const size_t off = up16(image_.size());
+		image_.resize(off + bytes, 0);
+		if (bytes) std::memcpy(image_.data() + off, src, bytes);
+		return off;
+	}
+	template <class T>
+	size_t add(const std::vector<T> &v) { return add(v.data(), v.size() * sizeof(T)); }
+	// The image into `buf` on the current device (DevBuf::upload); at() then gives device pointers.
+	int upload(DevBuf &buf, const std::string &what) {
+		image_.resize(up16(image_.size()) + 16, 0);
+		if (int rc = buf.upload(image_.data(), image_.size(), what)) return rc;
+		base_ = buf.as<unsigned char>();
+		return MBIK_OK;
+	}
+	template <class T>
+	const T *at(size_t off) const { return reinterpret_cast<const T *>(base_ + off); }
+
+private:
+	static size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
+	std::vector<unsigned char> image_;
+	const unsigned char *base_ = nullptr;
 };
 
 // The layout settings a caller may pin (mbik_plan_set_*), saved with the plan, and what an
@@ -272,6 +309,34 @@ size_t cmode_dirty_bytes(const mbik::HostPlan &h);
 size_t cmode_file_node_bytes(const mbik::HostPlan &h);
 std::vector<float> cmode_nodes_tiled(const mbik::HostPlan &h, const float *plain);
 void cmode_nodes_plain(const mbik::HostPlan &h, const float *tiled, float *plain);
+
+// ---- the pieces the animation entries (host_clip.cpp, host_playback.cpp) compose their call checks from ----
+// A call check returns 0 to go on, kNothingToDo for a call that is valid and empty, or a refusal (< 0); settled() is what
+// the entry returns for the last two.  Each piece is MBIK_OK or its refusal, and builds its text only when it refuses.
+constexpr int kNothingToDo = 1;
+inline int settled(int rc) { return rc < 0 ? rc : MBIK_OK; }
+inline int check_count(int32_t count) { return count < 0 ? fail(MBIK_EINVAL, "negative count") : MBIK_OK; }
+int check_layer_count(int32_t layer_count); // [1, MBIK_CLIP_MAX_LAYERS]
+inline int check_flags(uint32_t flags, uint32_t known) {
+	return flags & ~known ? fail(MBIK_EINVAL, "unknown flags " + std::to_string(flags)) : MBIK_OK;
+}
+inline int check_given(const void *p, const char *name) { return p ? MBIK_OK : fail(MBIK_EINVAL, std::string("null ") + name); }
+inline int check_aligned8(const void *p, const char *name) {
+	return reinterpret_cast<uintptr_t>(p) % 8 ? fail(MBIK_EINVAL, std::string(name) + " is not 8-byte aligned") : MBIK_OK;
+}
+inline int check_apart(const void *in, size_t n_in, const char *in_name, const void *out, size_t n_out, const char *out_name) {
+	return overlap(in, n_in, out, n_out) ? fail(MBIK_EINVAL, std::string(out_name) + " overlaps " + in_name) : MBIK_OK;
+}
+// The tail of a device entry: launch() with `device` current, its error as MBIK_EHIP "<what> launch failed: <HIP's text>".
+template <class Launch>
+int launched(int device, const char *what, Launch launch) {
+	DeviceGuard guard(device);
+	const hipError_t e = launch();
+	if (e != hipSuccess) return fail(MBIK_EHIP, std::string(what) + " launch failed: " + hipGetErrorString(e));
+	return MBIK_OK;
+}
+// A clip's length and loop mode (mbik_clipset_create's test; `where`: "clip <c>").
+int check_clip(const mbik_clip_desc &d, const std::string &where);
 
 // What a playback object takes from a clip set at its creation (host_clip.cpp): the set's device and each clip's
 // length and loop mode, read back from the set's tables.

@@ -46,9 +46,7 @@ int ensure_fk_schedule(mbik_plan *p) {
 	}
 	// published only once the copy succeeded: a failed call leaves nothing behind
 	DevBuf d;
-	if (int rc = d.reserve(blob.size() * sizeof(int32_t), "hipMalloc failed for the bone schedule")) return rc;
-	if (hipMemcpy(d.as<void>(), blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
-		return fail(MBIK_EHIP, "hipMemcpy failed for the bone schedule");
+	if (int rc = d.upload(blob.data(), blob.size() * sizeof(int32_t), "the bone schedule")) return rc;
 	p->device_bytes += (int64_t)d.bytes();
 	p->fk_levels = levels;
 	p->fk_sched = std::move(d);

@@ -38,8 +38,6 @@ static_assert(MBIK_PLAYBACK_STARTED == mbik::kPlaybackStarted && MBIK_PLAYBACK_E
 
 namespace {
 
-size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 // The desc against the clip count: what the per-skeleton code indexes without a test.
 int check_desc(int32_t clip_count, const mbik_playback_desc *desc) {
 	if (!desc) return MBIK_OK;
@@ -88,34 +86,29 @@ mbik::PlaybackSlot stored(const mbik_playback_slot &r, int j) {
 	return mbik::PlaybackSlot{r.pos, r.clip, r.speed, j ? r.blend_left : 0.0f, j ? r.blend_time : 0.0f};
 }
 
-// The checks of an advance past the object's own; 0 = go on, 1 = nothing to do.
+// The checks of an advance past the object's own.
 int check_advance(int32_t count, int32_t K, double delta, float speed_scale, const mbik_playback_cmd *cmds, int32_t cmd_count,
 		const mbik_clip_layer *layers_out, const double *time_prev_out, const uint8_t *events_out) {
 	if (!std::isfinite(delta)) return fail(MBIK_EINVAL, "delta is not finite");
 	if (!std::isfinite(speed_scale)) return fail(MBIK_EINVAL, "speed_scale is not finite");
 	if (cmd_count < 0) return fail(MBIK_EINVAL, "negative cmd_count");
-	if (count == 0) return 1;
-	if (!layers_out) return fail(MBIK_EINVAL, "null layers_out");
-	if (!time_prev_out) return fail(MBIK_EINVAL, "null time_prev_out");
-	if (cmd_count > 0 && !cmds) return fail(MBIK_EINVAL, "null cmds");
-	if (reinterpret_cast<uintptr_t>(layers_out) % 8) return fail(MBIK_EINVAL, "layers_out is not 8-byte aligned");
-	if (reinterpret_cast<uintptr_t>(time_prev_out) % 8) return fail(MBIK_EINVAL, "time_prev_out is not 8-byte aligned");
-	if (cmd_count > 0 && reinterpret_cast<uintptr_t>(cmds) % 8) return fail(MBIK_EINVAL, "cmds is not 8-byte aligned");
+	if (count == 0) return kNothingToDo;
+	if (int rc = check_given(layers_out, "layers_out")) return rc;
+	if (int rc = check_given(time_prev_out, "time_prev_out")) return rc;
+	const bool with_cmds = cmd_count > 0; // cmds is not looked at without
+	if (int rc = with_cmds ? check_given(cmds, "cmds") : MBIK_OK) return rc;
+	if (int rc = check_aligned8(layers_out, "layers_out")) return rc;
+	if (int rc = check_aligned8(time_prev_out, "time_prev_out")) return rc;
+	if (int rc = with_cmds ? check_aligned8(cmds, "cmds") : MBIK_OK) return rc;
 	const size_t per = (size_t)count * K, nl = per * sizeof(mbik_clip_layer), np = per * sizeof(double), ne = (size_t)count,
 				 nc = (size_t)cmd_count * sizeof(mbik_playback_cmd);
-	if (overlap(layers_out, nl, time_prev_out, np)) return fail(MBIK_EINVAL, "time_prev_out overlaps layers_out");
-	if (events_out && overlap(layers_out, nl, events_out, ne)) return fail(MBIK_EINVAL, "events_out overlaps layers_out");
-	if (events_out && overlap(time_prev_out, np, events_out, ne)) return fail(MBIK_EINVAL, "events_out overlaps time_prev_out");
-	if (cmd_count > 0 && overlap(cmds, nc, layers_out, nl)) return fail(MBIK_EINVAL, "layers_out overlaps cmds");
-	if (cmd_count > 0 && overlap(cmds, nc, time_prev_out, np)) return fail(MBIK_EINVAL, "time_prev_out overlaps cmds");
-	if (cmd_count > 0 && events_out && overlap(cmds, nc, events_out, ne)) return fail(MBIK_EINVAL, "events_out overlaps cmds");
+	if (int rc = check_apart(layers_out, nl, "layers_out", time_prev_out, np, "time_prev_out")) return rc;
+	if (int rc = events_out ? check_apart(layers_out, nl, "layers_out", events_out, ne, "events_out") : MBIK_OK) return rc;
+	if (int rc = events_out ? check_apart(time_prev_out, np, "time_prev_out", events_out, ne, "events_out") : MBIK_OK) return rc;
+	if (int rc = with_cmds ? check_apart(cmds, nc, "cmds", layers_out, nl, "layers_out") : MBIK_OK) return rc;
+	if (int rc = with_cmds ? check_apart(cmds, nc, "cmds", time_prev_out, np, "time_prev_out") : MBIK_OK) return rc;
+	if (int rc = with_cmds && events_out ? check_apart(cmds, nc, "cmds", events_out, ne, "events_out") : MBIK_OK) return rc;
 	return 0;
-}
-
-int check_layer_count(int32_t K) {
-	if (K < 1 || K > MBIK_CLIP_MAX_LAYERS)
-		return fail(MBIK_EINVAL, "layer_count " + std::to_string(K) + " outside [1, " + std::to_string(MBIK_CLIP_MAX_LAYERS) + "]");
-	return MBIK_OK;
 }
 
 int check_range(const mbik_playback *pb, int32_t first, int32_t n, const void *slots, const void *flags) {
@@ -175,19 +168,15 @@ int32_t mbik_playback_create(mbik_clipset *set, int32_t capacity, int32_t layer_
 	if (int rc = check_desc(cc, desc)) return rc;
 	pb->capacity = capacity, pb->K = layer_count;
 	DeviceGuard guard(pb->device);
-	// the tables: clip infos, next, blend_times, each from a 16-byte boundary
-	const size_t n_info = (size_t)cc * sizeof(mbik::ClipInfo), n_next = desc && desc->next ? (size_t)cc * sizeof(int32_t) : 0,
-				 n_bt = desc && desc->blend_times ? (size_t)cc * cc * sizeof(float) : 0;
-	const size_t o_info = 0, o_next = up16(o_info + n_info), o_bt = up16(o_next + n_next), t_bytes = up16(o_bt + n_bt) + 16;
-	std::vector<unsigned char> tb(t_bytes, 0);
-	std::memcpy(tb.data() + o_info, pb->clips.data(), n_info);
-	if (n_next) std::memcpy(tb.data() + o_next, desc->next, n_next);
-	if (n_bt) std::memcpy(tb.data() + o_bt, desc->blend_times, n_bt);
-	if (int rc = pb->tables.reserve(t_bytes, "hipMalloc failed for the playback tables")) return rc;
-	unsigned char *t = pb->tables.as<unsigned char>();
-	if (hipMemcpy(t, tb.data(), t_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(MBIK_EHIP, "hipMemcpy failed for the playback tables");
-	pb->tab = mbik::PlaybackTables{cc, desc ? desc->default_blend_time : 0.0f, reinterpret_cast<const mbik::ClipInfo *>(t + o_info),
-			n_next ? reinterpret_cast<const int32_t *>(t + o_next) : nullptr, n_bt ? reinterpret_cast<const float *>(t + o_bt) : nullptr};
+	// the tables: clip infos, next, blend_times; a table the desc leaves out is an empty section and a null pointer
+	const int32_t *next = desc ? desc->next : nullptr;
+	const float *blend_times = desc ? desc->blend_times : nullptr;
+	Blob t;
+	const size_t o_info = t.add(pb->clips), o_next = t.add(next, next ? (size_t)cc * sizeof(int32_t) : 0),
+				 o_bt = t.add(blend_times, blend_times ? (size_t)cc * cc * sizeof(float) : 0);
+	if (int rc = t.upload(pb->tables, "the playback tables")) return rc;
+	pb->tab = mbik::PlaybackTables{cc, desc ? desc->default_blend_time : 0.0f, t.at<mbik::ClipInfo>(o_info),
+			next ? t.at<int32_t>(o_next) : nullptr, blend_times ? t.at<float>(o_bt) : nullptr};
 	// the state: every slot off
 	mbik::PlaybackState st{nullptr, ((int64_t)capacity + 3) & ~(int64_t)3, layer_count};
 	const size_t s_bytes = st.bytes() + 16;
@@ -222,13 +211,11 @@ int32_t mbik_playback_advance(mbik_playback *pb, int32_t count, double delta, fl
 		mbik_clip_layer *layers_out, double *time_prev_out, uint8_t *events_out, void *hip_stream) {
 	if (!pb) return fail(MBIK_EINVAL, "null playback object");
 	if (count < 0 || count > pb->capacity) return fail(MBIK_EINVAL, "count " + std::to_string(count) + " outside [0, " + std::to_string(pb->capacity) + "]");
-	const int rc = check_advance(count, pb->K, delta, speed_scale, cmds, cmd_count, layers_out, time_prev_out, events_out);
-	if (rc) return rc < 0 ? rc : MBIK_OK;
-	DeviceGuard guard(pb->device);
-	hipError_t e = mbik::launch_playback(reinterpret_cast<hipStream_t>(hip_stream), pb->tab, pb->st, count, pb->K, delta, speed_scale,
-			reinterpret_cast<const mbik::PlaybackCmd *>(cmds), cmd_count, reinterpret_cast<mbik::ClipLayer *>(layers_out), time_prev_out, events_out);
-	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("playback advance launch failed: ") + hipGetErrorString(e));
-	return MBIK_OK;
+	if (int rc = check_advance(count, pb->K, delta, speed_scale, cmds, cmd_count, layers_out, time_prev_out, events_out)) return settled(rc);
+	return launched(pb->device, "playback advance", [&] {
+		return mbik::launch_playback(reinterpret_cast<hipStream_t>(hip_stream), pb->tab, pb->st, count, pb->K, delta, speed_scale,
+				reinterpret_cast<const mbik::PlaybackCmd *>(cmds), cmd_count, reinterpret_cast<mbik::ClipLayer *>(layers_out), time_prev_out, events_out);
+	});
 }
 
 int32_t mbik_playback_advance_cpu(int32_t clip_count, const mbik_clip_desc *clips, const mbik_playback_desc *desc, int32_t count,
@@ -238,19 +225,15 @@ int32_t mbik_playback_advance_cpu(int32_t clip_count, const mbik_clip_desc *clip
 	if (!clips) return fail(MBIK_EINVAL, "null clips");
 	std::vector<mbik::ClipInfo> info((size_t)clip_count);
 	for (int32_t c = 0; c < clip_count; c++) {
-		const mbik_clip_desc &d = clips[c];
-		const std::string where = "clip " + std::to_string(c);
-		if (!(d.length > 0) || !std::isfinite(d.length)) return fail(MBIK_EINVAL, where + ": length must be positive and finite");
-		if (d.loop_mode != 0 && d.loop_mode != 1) return fail(MBIK_EINVAL, where + ": unknown loop_mode " + std::to_string(d.loop_mode));
-		info[c] = mbik::ClipInfo{d.length, d.loop_mode, 0};
+		if (int rc = check_clip(clips[c], "clip " + std::to_string(c))) return rc;
+		info[c] = mbik::ClipInfo{clips[c].length, clips[c].loop_mode, 0};
 	}
 	if (int rc = check_desc(clip_count, desc)) return rc;
-	if (count < 0) return fail(MBIK_EINVAL, "negative count");
+	if (int rc = check_count(count)) return rc;
 	if (int rc = check_layer_count(layer_count)) return rc;
 	if (count > 0 && (!slots || !flags)) return fail(MBIK_EINVAL, "null slots or flags");
 	if (int rc = check_state(info, count, layer_count, slots, flags)) return rc;
-	const int rc = check_advance(count, layer_count, delta, speed_scale, cmds, cmd_count, layers_out, time_prev_out, events_out);
-	if (rc) return rc < 0 ? rc : MBIK_OK;
+	if (int rc = check_advance(count, layer_count, delta, speed_scale, cmds, cmd_count, layers_out, time_prev_out, events_out)) return settled(rc);
 	const mbik::PlaybackTables T{clip_count, desc ? desc->default_blend_time : 0.0f, info.data(), desc ? desc->next : nullptr,
 			desc ? desc->blend_times : nullptr};
 	mbik::PlaybackSlot *S = reinterpret_cast<mbik::PlaybackSlot *>(slots);

@@ -189,9 +189,7 @@ int create_mesh(int32_t bone_count, int32_t vertex_count, int32_t influences, co
 		mbik::skin_pack(vertex_count, influences, positions, normals, bone_indices, weights, packed.data());
 		if (shaped) mbik::morph_pack(vertex_count, influences, m->P, shapes->positions, shapes->normals, packed.data());
 		if (tangents) mbik::tangent_pack(vertex_count, influences, m->P, tangents, shape_tangents, packed.data());
-		if (int rc = m->mesh.reserve(packed.size(), "hipMalloc failed for the mesh")) return rc;
-		if (hipMemcpy(m->mesh.as<void>(), packed.data(), packed.size(), hipMemcpyHostToDevice) != hipSuccess)
-			return fail(MBIK_EHIP, "hipMemcpy failed for the mesh");
+		if (int rc = m->mesh.upload(packed.data(), packed.size(), "the mesh")) return rc;
 	}
 	// the bone boxes (bounds.h): a table of their own, the used bones only
 	m->bone_boxes.resize((size_t)bone_count * 6), m->bone_used.resize((size_t)bone_count);
@@ -200,9 +198,7 @@ int create_mesh(int32_t bone_count, int32_t vertex_count, int32_t influences, co
 	if (m->used_bones > 0) {
 		std::vector<unsigned char> table((size_t)m->used_bones * mbik::kBoneRecordBytes);
 		mbik::bone_table_pack(bone_count, m->bone_boxes.data(), m->bone_used.data(), table.data());
-		if (int rc = m->bone_table.reserve(table.size(), "hipMalloc failed for the mesh's bone boxes")) return rc;
-		if (hipMemcpy(m->bone_table.as<void>(), table.data(), table.size(), hipMemcpyHostToDevice) != hipSuccess)
-			return fail(MBIK_EHIP, "hipMemcpy failed for the mesh's bone boxes");
+		if (int rc = m->bone_table.upload(table.data(), table.size(), "the mesh's bone boxes")) return rc;
 	}
 	*out_mesh = m.release();
 	return MBIK_OK;

@@ -1,5 +1,7 @@
-// mbik_clip_sample's kernel: Godot's Animation track interpolation for a batch of skeletons, each
-// at its own time in its own clip (clip.h).
+// mbik_clip_sample's and mbik_clip_sample_layers' kernels, two per-bone calls in one frame.
+//
+// mbik_clip_sample: Godot's Animation track interpolation for a batch of skeletons, each at its own
+// time in its own clip (clip.h).
 //
 // One thread per bone; a block owns kClipThreads consecutive bones of the batch, whatever
 // skeletons they belong to, as k_blend.hip does.  A lane builds its bone's 10 floats in LDS, and
@@ -14,7 +16,23 @@
 // clamped or nearest skips them.
 //
 // The kernel tests no key index: mbik_clipset_create has checked every table (host_clip.cpp).
-#include "clip.h"
+//
+// mbik_clip_sample_layers: AnimationMixer's blend of up to 8 clips a skeleton, each at its own time
+// with its own weight, accumulated onto the rest pose (clip_layers.h).
+//
+// The same frame.  The inputs are 16 bytes a layer and the clip set's tables, which stay in L2.
+// The layers are walked in a loop over named state -- K is uniform over the launch but not a
+// compile-time constant, and a per-thread array indexed by it would live in scratch.  The loop
+// loads layer l + 1's record, clip info and three headers before it consumes layer l's search
+// steps, so a lane has two layers' loads in flight; what bounds the sampler is the rate of its own
+// L2 requests (§16), not arithmetic.  The slerp, the lerps and every key load sit behind per-lane
+// branches: a layer that is off, untracked or weighted zero -- most layers of a crowd that is not
+// mid-transition -- costs its record and headers only.
+//
+// The layered kernel tests every clip index before it touches a table (the records are device data
+// the host never sees), and no key index either.
+#include "batch_lane.h"
+#include "clip_layers.h"
 #include "kernels.h"
 #include "lds_copy.h"
 
@@ -23,25 +41,36 @@ using namespace mbik;
 
 constexpr int kClipThreads = 256;
 
-// LV: the set's libm_variant (gd::LIBM_FMA / LIBM_SSE2), a compile-time constant of sin_f.
-template <int LV>
-__global__ __launch_bounds__(kClipThreads) void mbik_clip_kernel(ClipView v, int64_t total, const double *time, const int32_t *clip_index,
-		int clip, float *pose_out) {
+// The frame: per_bone(skeleton, bone, out) builds one bone's record in the block's LDS tile.
+template <class PerBone>
+__device__ __forceinline__ void clip_frame(int B, int64_t total, float *pose_out, PerBone per_bone) {
 	__shared__ __attribute__((aligned(16))) float Pl[kClipThreads * 10];
 	const int64_t b0 = (int64_t)blockIdx.x * kClipThreads;
 	const int n = (int)min((int64_t)kClipThreads, total - b0);
 	if (n <= 0) return;
 	const int t = threadIdx.x;
 	if (t < n) {
-		// the skeleton of bone b0 + t: the block's first skeleton (uniform) plus a 32-bit quotient
-		const uint32_t B = (uint32_t)v.B;
-		const int64_t s0 = b0 / v.B;
-		const uint32_t r = (uint32_t)(b0 - s0 * v.B) + (uint32_t)t, q = r / B;
-		const int64_t s = s0 + q;
-		clip_sample_bone(v, clip_index ? clip_index[s] : clip, (int)(r - q * B), time[s], LV, Pl + t * 10);
+		const BatchLane ln = batch_lane(B, b0, t);
+		per_bone(ln.s, ln.item, Pl + t * 10);
 	}
 	__syncthreads();
 	lds_copy_runs<false, kClipThreads>(Pl, 0, pose_out + b0 * 10, n * 10, 1);
+}
+
+// LV: the set's libm_variant (gd::LIBM_FMA / LIBM_SSE2), a compile-time constant of sin_f.
+template <int LV>
+__global__ __launch_bounds__(kClipThreads) void mbik_clip_kernel(ClipView v, int64_t total, const double *time, const int32_t *clip_index,
+		int clip, float *pose_out) {
+	clip_frame(v.B, total, pose_out,
+			[&](int64_t s, int bone, float *out) { clip_sample_bone(v, clip_index ? clip_index[s] : clip, bone, time[s], LV, out); });
+}
+
+// (An occupancy target of 4 waves a SIMD holds the allocation at 128 VGPRs without a spill, and
+// measured the same time as the 136-140 VGPRs and 3 waves the compiler picks on its own: §20.)
+template <int LV>
+__global__ __launch_bounds__(kClipThreads) void mbik_clip_layers_kernel(ClipView v, int64_t total, const ClipLayer *layers, int K,
+		uint32_t flags, float *pose_out) {
+	clip_frame(v.B, total, pose_out, [&](int64_t s, int bone, float *out) { clip_layers_bone(v, layers + s * K, K, flags, bone, LV, out); });
 }
 } // namespace
 
@@ -52,6 +81,14 @@ hipError_t launch_clip(hipStream_t st, const ClipView &v, int libm, int64_t tota
 	const unsigned blocks = (unsigned)((total_bones + kClipThreads - 1) / kClipThreads);
 	const auto kernel = libm == LIBM_SSE2 ? mbik_clip_kernel<LIBM_SSE2> : mbik_clip_kernel<LIBM_FMA>;
 	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kClipThreads), 0, st, v, total_bones, time, clip_index, clip, pose_out);
+	return hipGetLastError();
+}
+
+hipError_t launch_clip_layers(hipStream_t st, const ClipView &v, int libm, int64_t total_bones, const ClipLayer *layers, int layer_count,
+		uint32_t flags, float *pose_out) {
+	const unsigned blocks = (unsigned)((total_bones + kClipThreads - 1) / kClipThreads);
+	const auto kernel = libm == LIBM_SSE2 ? mbik_clip_layers_kernel<LIBM_SSE2> : mbik_clip_layers_kernel<LIBM_FMA>;
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kClipThreads), 0, st, v, total_bones, layers, layer_count, flags, pose_out);
 	return hipGetLastError();
 }
 

@@ -15,6 +15,7 @@
 //
 // The kernels test every clip index before they touch a table (the indices are device data the
 // host never sees), and no key index: mbik_clipset_create_shaped has checked every table.
+#include "batch_lane.h"
 #include "clip_shapes.h"
 #include "kernels.h"
 
@@ -23,26 +24,13 @@ using namespace mbik;
 
 constexpr int kShapeThreads = 256;
 
-// The skeleton and the shape of weight b0 + t: the block's first skeleton (uniform, one 64-bit
-// division) plus a 32-bit quotient per lane.
-struct ShapeLane {
-	int64_t s;
-	int shape;
-};
-__device__ __forceinline__ ShapeLane shape_lane(int P, int64_t b0, int t) {
-	const uint32_t Pu = (uint32_t)P;
-	const int64_t s0 = b0 / P;
-	const uint32_t r = (uint32_t)(b0 - s0 * P) + (uint32_t)t, q = r / Pu;
-	return ShapeLane{s0 + q, (int)(r - q * Pu)};
-}
-
 __global__ __launch_bounds__(kShapeThreads) void mbik_clip_shapes_kernel(ShapeView v, int64_t total, const double *time,
 		const int32_t *clip_index, int clip, float *weights_out) {
 	const int64_t b0 = (int64_t)blockIdx.x * kShapeThreads;
 	const int t = threadIdx.x;
 	if (b0 + t >= total) return;
-	const ShapeLane ln = shape_lane(v.P, b0, t);
-	weights_out[b0 + t] = shape_sample(v, clip_index ? clip_index[ln.s] : clip, ln.shape, time[ln.s]);
+	const BatchLane ln = batch_lane(v.P, b0, t);
+	weights_out[b0 + t] = shape_sample(v, clip_index ? clip_index[ln.s] : clip, ln.item, time[ln.s]);
 }
 
 __global__ __launch_bounds__(kShapeThreads) void mbik_clip_shapes_layers_kernel(ShapeView v, int64_t total, const ClipLayer *layers, int K,
@@ -50,8 +38,8 @@ __global__ __launch_bounds__(kShapeThreads) void mbik_clip_shapes_layers_kernel(
 	const int64_t b0 = (int64_t)blockIdx.x * kShapeThreads;
 	const int t = threadIdx.x;
 	if (b0 + t >= total) return;
-	const ShapeLane ln = shape_lane(v.P, b0, t);
-	weights_out[b0 + t] = shape_layers(v, layers + ln.s * K, K, flags, ln.shape);
+	const BatchLane ln = batch_lane(v.P, b0, t);
+	weights_out[b0 + t] = shape_layers(v, layers + ln.s * K, K, flags, ln.item);
 }
 } // namespace
 

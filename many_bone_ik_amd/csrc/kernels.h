@@ -219,7 +219,7 @@ hipError_t launch_blend(hipStream_t st, int64_t total_bones, int B, int libm, fl
 struct ClipView;
 hipError_t launch_clip(hipStream_t st, const ClipView &v, int libm, int64_t total_bones, const double *time, const int32_t *clip_index,
 		int clip, float *pose_out);
-// k_clip_layers.hip: mbik_clip_sample_layers (clip_layers.h).  The same shape; layers is device memory, [count][layer_count]
+// k_clip.hip: mbik_clip_sample_layers (clip_layers.h).  The same shape; layers is device memory, [count][layer_count]
 // records of 16 bytes, 8-byte aligned; layer_count in [1, 8]; the kernel tests every record's clip index itself.
 struct ClipLayer;
 hipError_t launch_clip_layers(hipStream_t st, const ClipView &v, int libm, int64_t total_bones, const ClipLayer *layers, int layer_count,

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 SENTINEL = np.uint32(0x4B1D4B1D).view(np.float32)   # a finite float no sample produces
 GUARD = 16                                           # guard skeletons on each side of the output and of the layer array
 GUARD_LAYER = (0.4242, 1, 1.0)                       # a record that would sample something else, were it read
-BLOCK = 256                                          # bones a block (k_clip_layers.hip)
+BLOCK = 256                                          # bones a block (k_clip.hip)
 LAYER_COUNTS = (1, 2, 3, 8)
 
 

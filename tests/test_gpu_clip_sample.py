@@ -99,7 +99,7 @@ def assert_same(got, want, what=""):
 
 # (bones, count): 1 bone in all; one block exactly (two ways); one block + 1; several blocks with a
 # ragged tail, at every bone count; bones = 7: a block spans 36 skeletons, each with its own time and clip
-SHAPES = [(1, 1), (1, BLOCK), (32, BLOCK // 32), (1, BLOCK + 1), (3, 300), (7, 150), (33, 20), (200, 7)]
+SHAPES = [(1, 1), (1, 5), (1, BLOCK), (32, BLOCK // 32), (1, BLOCK + 1), (3, 300), (7, 150), (33, 20), (200, 7)]
 
 
 @pytest.mark.parametrize("B,n", SHAPES, ids=[f"{b}x{n}" for b, n in SHAPES])
@@ -114,6 +114,25 @@ def test_device_matches_cpu_entry(sets, torch_dev, B, n):
     for clip in range(len(clips)):
         assert_same(device_sample(torch, dev, cs, B, t, None, clip=clip), A.clip_sample_cpu(B, rest, clips, t, clip=clip),
                     f"scalar clip {clip}")
+
+
+@pytest.mark.parametrize("B", (1, 3))
+def test_a_set_without_any_track(mbik, torch_dev, B):
+    """The tables' edge layout: no clip has a track, so the key sections hold the spare record only and every header is
+    empty; every pose is the rest pose, on the device as on the host."""
+    torch, dev = torch_dev
+    rest = A.synthetic_clips(300 + B, B)[0]
+    clips = [dict(length=1.5, loop_mode=A.LOOP_LINEAR, tracks=[]), dict(length=0.5, loop_mode=A.LOOP_NONE, tracks=[])]
+    t, ci = np.array([0.0, 0.25, 0.75, 1.5, -2.0]), np.array([0, 1, 0, 1, 0], np.int32)
+    want = A.clip_sample_cpu(B, rest, clips, t, ci)
+    assert R.same_bits(want, np.tile(rest, (5, 1, 1)))
+    with A.ClipSet(B, rest, clips) as cs:
+        assert_same(device_sample(torch, dev, cs, B, t, ci), want, "no tracks")
+        layers = A.pack_layers(np.stack([t, t[::-1]], axis=1), np.stack([ci, 1 - ci], axis=1), np.full((5, 2), 0.5))
+        d_l, d_o = torch.from_numpy(layers.view(np.uint8).reshape(-1).copy()).to(dev), torch.zeros((5, B, 10), dtype=torch.float32, device=dev)
+        cs.sample_layers(d_l.data_ptr(), d_o.data_ptr(), 5, 2)
+        torch.cuda.synchronize()
+        assert R.same_bits(d_o.cpu().numpy(), A.clip_sample_layers_cpu(B, rest, clips, layers))
 
 
 def test_guard_entries_would_change_the_result(sets):

@@ -135,6 +135,21 @@ def test_layered_matches_cpu_entry(sets, torch_dev, P, n):
             assert_same(device_layers(torch, dev, cs, P, layers, flags), want, f"K={K} flags={flags}")
 
 
+def test_a_shaped_set_without_shape_tracks(mbik, torch_dev):
+    """The shape tables' edge layout: P = 1 and no shape track in any clip, so the key section holds the spare record only;
+    every weight is the shape's init, plain and layered, on the device as on the host."""
+    torch, dev = torch_dev
+    rest, clips = A.synthetic_clips(301, BONES)
+    init = np.array([0.625], np.float32)
+    t, ci = np.array([0.0, 0.3, 0.9, 2.5, -1.0]), np.array([0, 1, 2, 1, 0], np.int32)
+    want = A.clip_sample_shapes_cpu(1, clips, t, clip_index=ci, shape_init=init)
+    assert R.same_bits(want, np.full((5, 1), 0.625, np.float32))
+    with A.ClipSet(BONES, rest, clips, shape_count=1, shape_init=init) as cs:
+        assert_same(device_plain(torch, dev, cs, 1, t, ci), want, "no shape tracks")
+        layers = R.random_layers(5, 5, 2, clips, specials=False)
+        assert_same(device_layers(torch, dev, cs, 1, layers, 0), A.clip_sample_shapes_layers_cpu(1, clips, layers, 0, shape_init=init), "layered")
+
+
 def test_specials_are_in_the_batches_and_guards_would_change_the_result(sets):
     """The recipe's statistics of the 5 x 130 batches above: every branch is there; and were a guard
     entry read in place of a skeleton's own, its weights would differ."""

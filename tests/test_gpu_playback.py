@@ -102,6 +102,22 @@ def test_device_matches_cpu_entry(clipset, torch_dev, n):
         assert seen == 63, f"events seen {seen:#x}"
 
 
+@pytest.mark.parametrize("tables", (("next",), ("blend_times",), ()), ids=("next only", "blend_times only", "neither"))
+def test_tables_a_desc_leaves_out(clipset, torch_dev, tables):
+    """The tables' edge layouts: a desc with `next` only, with `blend_times` only, and none at all (an absent table is a null
+    pointer to the per-skeleton code), 5 skeletons through commands and clip ends."""
+    torch, dev = torch_dev
+    n, K = 5, 2
+    desc = {k: DESC[k] for k in tables}
+    st, fl = R.initial_state(40 + len(tables), n, K)
+    with A.Playback(clipset, n, K, **desc) as pb:
+        pb.write(st, fl)
+        for frame, cmds in enumerate(R.script(7, n, 8)):
+            lay, prev, ev = device_frame(torch, dev, pb, n, K, 0.25, 1.0, cmds, off=0)
+            st, fl, w_lay, w_prev, w_ev = A.playback_advance_cpu(R.CLIPS, st, fl, 0.25, 1.0, cmds=cmds, **desc)
+            assert_frame(f"{tables} frame={frame}", (*pb.read(), lay, prev, ev), (st, fl, w_lay, w_prev, w_ev))
+
+
 def test_write_and_read_a_sub_range(clipset, torch_dev):
     K, cap = 3, 200
     st, fl = R.initial_state(5, cap, K)
