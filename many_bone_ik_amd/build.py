@@ -22,8 +22,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmbik.so")
 # kernel families first (the longest compiles start first)
-SOURCES = ["k_solve_w1.hip", "k_solve_w2.hip", "k_cmode.hip", "k_solve_rw.hip", "host_selftest.cpp", "k_aux.hip", "k_fk.hip", "k_skin.hip", "k_skin_list.hip", "k_bounds.hip", "k_cull_lod.hip", "k_blend.hip", "k_clip.hip", "k_clip_shapes.hip", "k_root_motion.hip", "k_playback.hip", "host_plan.cpp",
-           "host_topo_io.cpp", "host_autotune.cpp", "host_multi.cpp", "host_fk.cpp", "host_skin.cpp", "host_bounds.cpp", "host_lod.cpp", "host_blend.cpp", "host_clip.cpp", "host_playback.cpp", "plan.cpp"]
+SOURCES = ["k_solve_w1.hip", "k_solve_w2.hip", "k_cmode.hip", "k_solve_rw.hip", "host_selftest.cpp", "k_aux.hip", "k_fk.hip", "k_skin.hip", "k_skin_list.hip", "k_bounds.hip", "k_blend.hip", "k_clip.hip", "k_clip_shapes.hip", "k_root_motion.hip", "k_playback.hip", "host_plan.cpp",
+           "host_topo_io.cpp", "host_autotune.cpp", "host_multi.cpp", "host_fk.cpp", "host_skin.cpp", "host_bounds.cpp", "host_blend.cpp", "host_clip.cpp", "host_playback.cpp", "plan.cpp"]
 OBJ = os.path.join(HERE, "..", "build", "obj")
 STAMP = OUT + ".sha256"
 

@@ -9,6 +9,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -310,7 +311,8 @@ size_t cmode_file_node_bytes(const mbik::HostPlan &h);
 std::vector<float> cmode_nodes_tiled(const mbik::HostPlan &h, const float *plain);
 void cmode_nodes_plain(const mbik::HostPlan &h, const float *tiled, float *plain);
 
-// ---- the pieces the animation entries (host_clip.cpp, host_playback.cpp) compose their call checks from ----
+// ---- the pieces the animation and mesh entries (host_clip.cpp, host_playback.cpp, host_skin.cpp, host_bounds.cpp) compose their call
+// checks from ----
 // A call check returns 0 to go on, kNothingToDo for a call that is valid and empty, or a refusal (< 0); settled() is what
 // the entry returns for the last two.  Each piece is MBIK_OK or its refusal, and builds its text only when it refuses.
 constexpr int kNothingToDo = 1;
@@ -327,13 +329,34 @@ inline int check_aligned8(const void *p, const char *name) {
 inline int check_apart(const void *in, size_t n_in, const char *in_name, const void *out, size_t n_out, const char *out_name) {
 	return overlap(in, n_in, out, n_out) ? fail(MBIK_EINVAL, std::string(out_name) + " overlaps " + in_name) : MBIK_OK;
 }
-// The tail of a device entry: launch() with `device` current, its error as MBIK_EHIP "<what> launch failed: <HIP's text>".
+// A buffer of a call by its name in the entry's signature; a null one is in nobody's way.
+struct Range {
+	const void *p;
+	size_t n;
+	const char *name;
+};
+// Every output apart from every input and from the outputs in front of it, an output at a time: "<output> overlaps <other>".
+inline int check_disjoint(std::initializer_list<Range> outputs, std::initializer_list<Range> inputs) {
+	for (const Range *o = outputs.begin(); o != outputs.end(); o++) {
+		if (!o->p) continue;
+		for (const Range &i : inputs)
+			if (i.p)
+				if (int rc = check_apart(i.p, i.n, i.name, o->p, o->n, o->name)) return rc;
+		for (const Range *q = outputs.begin(); q != o; q++)
+			if (q->p)
+				if (int rc = check_apart(q->p, q->n, q->name, o->p, o->n, o->name)) return rc;
+	}
+	return MBIK_OK;
+}
+// What a launch's error becomes: MBIK_EHIP "<what> launch failed: <HIP's text>".
+inline int launch_result(hipError_t e, const char *what) {
+	return e == hipSuccess ? MBIK_OK : fail(MBIK_EHIP, std::string(what) + " launch failed: " + hipGetErrorString(e));
+}
+// The tail of a device entry: launch() with `device` current.
 template <class Launch>
 int launched(int device, const char *what, Launch launch) {
 	DeviceGuard guard(device);
-	const hipError_t e = launch();
-	if (e != hipSuccess) return fail(MBIK_EHIP, std::string(what) + " launch failed: " + hipGetErrorString(e));
-	return MBIK_OK;
+	return launch_result(launch(), what);
 }
 // A clip's length and loop mode (mbik_clipset_create's test; `where`: "clip <c>").
 int check_clip(const mbik_clip_desc &d, const std::string &where);

@@ -34,11 +34,10 @@ int32_t mbik_pose_blend(mbik_plan *p, int32_t count, const float *pose_in, const
 	if (count == 0 || B == 0) return MBIK_OK;
 	if (int rc = check_args(count, B, pose_in, pose_mod, pose_out)) return rc;
 	if ((int64_t)count * B > (int64_t)INT32_MAX * 256) return fail(MBIK_EUNSUPPORTED, "more than 2^39 bones in one call");
-	DeviceGuard guard(p->device);
-	hipError_t e = mbik::launch_blend(reinterpret_cast<hipStream_t>(hip_stream), (int64_t)count * B, B, p->host.libm_variant, influence,
-			influence_per_skeleton, pose_in, pose_mod, pose_out);
-	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("pose blend launch failed: ") + hipGetErrorString(e));
-	return MBIK_OK;
+	return launched(p->device, "pose blend", [&] {
+		return mbik::launch_blend(reinterpret_cast<hipStream_t>(hip_stream), (int64_t)count * B, B, p->host.libm_variant, influence,
+				influence_per_skeleton, pose_in, pose_mod, pose_out);
+	});
 }
 
 int32_t mbik_pose_blend_cpu(int32_t bone_count, int32_t libm_variant, int32_t count, const float *pose_in, const float *pose_mod,

@@ -73,10 +73,10 @@ int32_t mbik_pose_globals(mbik_plan *p, int32_t count, const float *pose, const 
 	if (int rc = ensure_fk_schedule(p)) return rc;
 	const int64_t per = mbik::fk_lds_floats(B, 1) * (int64_t)sizeof(float);
 	const int S = (int)std::max<int64_t>(1, std::min<int64_t>({kFkBlockLdsTarget / per, kFkMaxSkeletonsPerBlock, count}));
-	hipError_t e = mbik::launch_fk(reinterpret_cast<hipStream_t>(hip_stream), count, B, P, S, p->fk_levels, p->fk_sched.as<int>(), pose,
-			inv_bind, globals, targets, pin_distance);
-	if (e != hipSuccess) return fail(MBIK_EHIP, std::string("pose globals launch failed: ") + hipGetErrorString(e));
-	return MBIK_OK;
+	// (the guard is this entry's own: the schedule's upload needs it too, and launched() would take a second one)
+	return launch_result(mbik::launch_fk(reinterpret_cast<hipStream_t>(hip_stream), count, B, P, S, p->fk_levels, p->fk_sched.as<int>(), pose,
+								 inv_bind, globals, targets, pin_distance),
+			"pose globals");
 }
 
 int32_t mbik_pose_globals_cpu(const mbik_skeleton_desc *desc, int32_t count, const float *pose, const float *inv_bind,

@@ -8,6 +8,8 @@
 // List-driven skinning (ABI 15, skin_list.h): mbik_skin_vertices_listed, which launches
 // k_skin_list.hip's kernels, and mbik_skin_vertices_listed_cpu.  The tangent stream and the struct-based call over
 // the three forms: mbik_mesh_create_desc, mbik_skin_vertices_call and mbik_skin_vertices_call_cpu.
+// Every skinning entry is one call of skin_on_device or skin_on_host: the older entries build the mbik_skin_call (and the
+// _cpu forms the mbik_mesh_desc) from their arguments and say which form they are.
 #include "host.h"
 
 #include "bounds.h"
@@ -69,82 +71,15 @@ SkinShape shape_of(const mbik_mesh *m, int64_t count, bool shaped) {
 	return sh;
 }
 
-// The argument checks of a skinning call past the mesh's own; 0 = launch, 1 = nothing to do.
-// out_rows: the outputs' rows where they are not `count` (the listed call's compact form; 0 = nothing to do).
-int check_call(int32_t B, int32_t V, bool mesh_normals, int32_t count, const float *skin, const float *out_positions,
-		const float *out_normals, int64_t out_rows = -1) {
-	if (count < 0) return fail(MBIK_EINVAL, "negative count");
-	if (out_normals && !mesh_normals) return fail(MBIK_EINVAL, "out_normals given for a mesh without normals");
-	if (count == 0 || V == 0 || out_rows == 0) return 1;
-	if (!skin) return fail(MBIK_EINVAL, "null skin");
-	if (!out_positions) return fail(MBIK_EINVAL, "null out_positions");
-	const size_t nskin = (size_t)count * B * 12 * sizeof(float), nout = (size_t)(out_rows < 0 ? count : out_rows) * V * 3 * sizeof(float);
-	if (overlap(skin, nskin, out_positions, nout)) return fail(MBIK_EINVAL, "out_positions overlaps skin");
-	if (out_normals && overlap(skin, nskin, out_normals, nout)) return fail(MBIK_EINVAL, "out_normals overlaps skin");
-	if (out_normals && overlap(out_positions, nout, out_normals, nout)) return fail(MBIK_EINVAL, "out_normals overlaps out_positions");
-	return 0;
-}
-
 // The shape checks mbik_mesh_create_shaped and mbik_skin_vertices_shaped_cpu share; lds_limit as morph_check's.
 int check_shapes(int32_t B, int32_t V, bool mesh_normals, const mbik_mesh_shapes *sh, int64_t lds_limit) {
-	if (!sh) return fail(MBIK_EINVAL, "null shapes");
+	if (int rc = check_given(sh, "shapes")) return rc;
 	if (sh->struct_size < (int32_t)sizeof(mbik_mesh_shapes)) return fail(MBIK_EINVAL, "mbik_mesh_shapes.struct_size is too small");
 	const mbik::MorphCheck c = mbik::morph_check(B, V, mesh_normals, sh->shape_count, sh->mode, sh->positions, sh->normals, lds_limit);
 	if (c == mbik::MORPH_TOO_LARGE)
 		return fail(MBIK_EUNSUPPORTED, "rig has " + std::to_string(B) + " bones and " + std::to_string(sh->shape_count) +
 				" shapes: " + mbik::morph_check_text(c) + " (MBIK_MAX_LDS_BYTES)");
 	if (c != mbik::MORPH_OK) return fail(MBIK_EINVAL, mbik::morph_check_text(c));
-	return MBIK_OK;
-}
-
-// The checks of a shaped call's weights, past check_call's; out_rows as there.
-int check_shape_weights(int32_t V, int32_t P, int32_t count, const float *shape_weights, const float *out_positions,
-		const float *out_normals, int64_t out_rows = -1) {
-	if (!shape_weights) return fail(MBIK_EINVAL, "null shape_weights");
-	const size_t nw = (size_t)count * P * sizeof(float), nout = (size_t)(out_rows < 0 ? count : out_rows) * V * 3 * sizeof(float);
-	if (overlap(shape_weights, nw, out_positions, nout)) return fail(MBIK_EINVAL, "out_positions overlaps shape_weights");
-	if (out_normals && overlap(shape_weights, nw, out_normals, nout)) return fail(MBIK_EINVAL, "out_normals overlaps shape_weights");
-	return MBIK_OK;
-}
-
-// The checks of a listed call (mbik_skin_vertices_listed and its _cpu form) past the mesh's and the shapes' own: everything
-// the plain or the shaped call refuses, with the outputs sized by the flag, and the list's own.  P: the mesh's shapes
-// (0: none).  0 = run, 1 = nothing to do.
-int check_listed(int32_t B, int32_t V, bool mesh_normals, int32_t P, int32_t count, const int32_t *indices, const int32_t *list_count,
-		int32_t max_list, const float *skin, const float *shape_weights, uint32_t flags, const float *out_positions,
-		const float *out_normals) {
-	if (flags & ~mbik::kSkinListFlags) return fail(MBIK_EINVAL, "unknown flag bits");
-	if (max_list < 0) return fail(MBIK_EINVAL, "negative max_list");
-	if (shape_weights && P < 1) return fail(MBIK_EINVAL, "shape_weights given for a mesh without shapes");
-	const int64_t rows = max_list == 0 ? 0 : ((flags & mbik::kSkinListCompact) ? max_list : count);
-	if (int rc = check_call(B, V, mesh_normals, count, skin, out_positions, out_normals, rows)) return rc;
-	if (shape_weights)
-		if (int rc = check_shape_weights(V, P, count, shape_weights, out_positions, out_normals, rows)) return rc;
-	if (!indices) return fail(MBIK_EINVAL, "null indices");
-	if (!list_count) return fail(MBIK_EINVAL, "null list_count");
-	const size_t nout = (size_t)rows * V * 3 * sizeof(float), nidx = (size_t)max_list * sizeof(int32_t);
-	for (const float *out : {out_positions, out_normals}) {
-		if (!out) continue;
-		const char *which = out == out_positions ? "out_positions" : "out_normals";
-		if (overlap(indices, nidx, out, nout)) return fail(MBIK_EINVAL, std::string(which) + " overlaps indices");
-		if (overlap(list_count, sizeof(int32_t), out, nout)) return fail(MBIK_EINVAL, std::string(which) + " overlaps list_count");
-	}
-	return 0;
-}
-
-// What the three device entry points do behind their checks: guard the mesh's device, pick the launch shape for
-// `tiled` skeletons or list entries, fill in what the mesh knows of `a` (the caller has set count, the buffers and, listed,
-// the list), launch.  A call with a.shape_weights is a shaped one.  failed: the error text's head.
-int launch_on_mesh(const mbik_mesh *m, void *hip_stream, int64_t tiled, mbik::SkinLaunch a, hipError_t (*launch)(const mbik::SkinLaunch &),
-		const char *failed) {
-	DeviceGuard guard(m->device);
-	const SkinShape sh = shape_of(m, tiled, a.shape_weights != nullptr);
-	a.st = reinterpret_cast<hipStream_t>(hip_stream);
-	a.K = m->K, a.mode = m->mode, a.B = m->B, a.V = m->V, a.P = m->P;
-	a.S = sh.S, a.chunk = sh.chunk, a.chunks = sh.chunks, a.vshift = sh.vshift;
-	a.mesh = m->mesh.as<unsigned char>(), a.mesh_normals = m->normals, a.mesh_tangents = m->tangents;
-	const hipError_t e = launch(a);
-	if (e != hipSuccess) return fail(MBIK_EHIP, std::string(failed) + hipGetErrorString(e));
 	return MBIK_OK;
 }
 
@@ -157,43 +92,62 @@ int check_tangents(const float *normals, const float *tangents, bool shaped, con
 	return MBIK_OK;
 }
 
-// mbik_mesh_create (shaped == false: `shapes` is not looked at), mbik_mesh_create_shaped and, with tangents [V][4] (and
-// shape_tangents [P][V][3] on a shaped mesh), mbik_mesh_create_desc.  Without tangents the device image is what it always was.
-int create_mesh(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions, const float *normals,
-		const int32_t *bone_indices, const float *weights, bool shaped, const mbik_mesh_shapes *shapes, int32_t device,
-		mbik_mesh **out_mesh, const float *tangents = nullptr, const float *shape_tangents = nullptr) {
+int check_desc_struct(const mbik_mesh_desc *d) {
+	if (int rc = check_given(d, "desc")) return rc;
+	if (d->struct_size < (int32_t)sizeof(mbik_mesh_desc)) return fail(MBIK_EINVAL, "mbik_mesh_desc.struct_size is too small");
+	return MBIK_OK;
+}
+
+int check_call_struct(const mbik_skin_call *c) {
+	if (int rc = check_given(c, "call")) return rc;
+	if (c->struct_size < (int32_t)sizeof(mbik_skin_call)) return fail(MBIK_EINVAL, "mbik_skin_call.struct_size is too small");
+	return MBIK_OK;
+}
+
+// The mesh arrays of the entries older than mbik_mesh_desc, as one.
+mbik_mesh_desc desc_of(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions, const float *normals,
+		const int32_t *bone_indices, const float *weights, const mbik_mesh_shapes *shapes = nullptr) {
+	return mbik_mesh_desc{(int32_t)sizeof(mbik_mesh_desc), bone_count, vertex_count, influences, positions, normals, nullptr, bone_indices,
+			weights, shapes, nullptr};
+}
+
+// mbik_mesh_create, mbik_mesh_create_shaped (need_shapes: a mesh without is refused) and mbik_mesh_create_desc.  Without
+// tangents the device image is what it always was.
+int create_mesh(const mbik_mesh_desc &d, bool need_shapes, int32_t device, mbik_mesh **out_mesh) {
 	if (!out_mesh) return fail(MBIK_EINVAL, "null out_mesh");
 	*out_mesh = nullptr;
+	const int32_t bone_count = d.bone_count, vertex_count = d.vertex_count, influences = d.influences;
+	const bool shaped = need_shapes || d.shapes;
 	if (influences != 4 && influences != 8) return fail(MBIK_EINVAL, mbik::skin_check_text(mbik::SKIN_BAD_INFLUENCES));
 	if (bone_count < 0 || vertex_count < 0) return fail(MBIK_EINVAL, mbik::skin_check_text(mbik::SKIN_NEGATIVE));
-	if (vertex_count > 0 && (!positions || !bone_indices || !weights)) return fail(MBIK_EINVAL, mbik::skin_check_text(mbik::SKIN_NULL));
+	if (vertex_count > 0 && (!d.positions || !d.bone_indices || !d.weights)) return fail(MBIK_EINVAL, mbik::skin_check_text(mbik::SKIN_NULL));
 	if (bone_count > mbik::kSkinMaxBones)
 		return fail(MBIK_EUNSUPPORTED, "rig has " + std::to_string(bone_count) + " bones; a mesh supports at most " +
 				std::to_string(mbik::kSkinMaxBones) + " (MBIK_SKIN_MAX_BONES: one skeleton's matrices must fit 160 KiB of LDS)");
 	if (shaped)
-		if (int rc = check_shapes(bone_count, vertex_count, normals != nullptr, shapes, mbik::kSkinMaxLdsBytes)) return rc;
-	if (int rc = check_tangents(normals, tangents, shaped, shape_tangents)) return rc;
-	if (int rc = check_mesh(bone_count, vertex_count, influences, positions, bone_indices, weights)) return rc;
+		if (int rc = check_shapes(bone_count, vertex_count, d.normals != nullptr, d.shapes, mbik::kSkinMaxLdsBytes)) return rc;
+	if (int rc = check_tangents(d.normals, d.tangents, shaped, d.shape_tangents)) return rc;
+	if (int rc = check_mesh(bone_count, vertex_count, influences, d.positions, d.bone_indices, d.weights)) return rc;
 	if (int rc = check_device(device)) return rc;
 	std::unique_ptr<mbik_mesh> m(new mbik_mesh());
-	m->device = device, m->B = bone_count, m->V = vertex_count, m->K = influences, m->normals = normals != nullptr;
-	m->tangents = tangents != nullptr;
-	if (shaped) m->P = shapes->shape_count, m->mode = shapes->mode;
+	m->device = device, m->B = bone_count, m->V = vertex_count, m->K = influences, m->normals = d.normals != nullptr;
+	m->tangents = d.tangents != nullptr;
+	if (shaped) m->P = d.shapes->shape_count, m->mode = d.shapes->mode;
 	DeviceGuard guard(device);
 	m->cu_count = cu_count_of(device);
 	if (vertex_count > 0) {
 		const mbik::SkinLayout l = mbik::skin_layout(vertex_count, influences, m->normals);
 		int64_t bytes = shaped ? mbik::morph_layout(vertex_count, influences, m->normals, m->P).bytes : l.bytes;
-		if (tangents) bytes = mbik::tangent_layout(vertex_count, influences, true, m->P, true).bytes;
+		if (d.tangents) bytes = mbik::tangent_layout(vertex_count, influences, true, m->P, true).bytes;
 		std::vector<unsigned char> packed((size_t)bytes);
-		mbik::skin_pack(vertex_count, influences, positions, normals, bone_indices, weights, packed.data());
-		if (shaped) mbik::morph_pack(vertex_count, influences, m->P, shapes->positions, shapes->normals, packed.data());
-		if (tangents) mbik::tangent_pack(vertex_count, influences, m->P, tangents, shape_tangents, packed.data());
+		mbik::skin_pack(vertex_count, influences, d.positions, d.normals, d.bone_indices, d.weights, packed.data());
+		if (shaped) mbik::morph_pack(vertex_count, influences, m->P, d.shapes->positions, d.shapes->normals, packed.data());
+		if (d.tangents) mbik::tangent_pack(vertex_count, influences, m->P, d.tangents, d.shape_tangents, packed.data());
 		if (int rc = m->mesh.upload(packed.data(), packed.size(), "the mesh")) return rc;
 	}
 	// the bone boxes (bounds.h): a table of their own, the used bones only
 	m->bone_boxes.resize((size_t)bone_count * 6), m->bone_used.resize((size_t)bone_count);
-	mbik::bone_boxes_build(bone_count, vertex_count, influences, positions, bone_indices, weights, m->bone_boxes.data(), m->bone_used.data());
+	mbik::bone_boxes_build(bone_count, vertex_count, influences, d.positions, d.bone_indices, d.weights, m->bone_boxes.data(), m->bone_used.data());
 	m->used_bones = mbik::bone_table_count(bone_count, m->bone_used.data());
 	if (m->used_bones > 0) {
 		std::vector<unsigned char> table((size_t)m->used_bones * mbik::kBoneRecordBytes);
@@ -204,53 +158,110 @@ int create_mesh(int32_t bone_count, int32_t vertex_count, int32_t influences, co
 	return MBIK_OK;
 }
 
-// ---- mbik_skin_vertices_call and its _cpu form ----
+// ---- a skinning call ----
+// What a call's checks need of the mesh: the handle's fields or the description's.
 struct MeshFacts {
 	int32_t B, V, P;
 	bool normals, tangents;
 };
+// Which entry a call came through.  kByCall (mbik_skin_vertices_call): the call's pointers say whether it is listed or
+// shaped.  The older entries are one form each; kShaped refuses a mesh without shapes and a missing shape_weights.
+enum SkinForm { kByCall, kPlain, kShaped, kListed };
 
-int check_call_struct(const mbik_skin_call *c) {
-	if (!c) return fail(MBIK_EINVAL, "null call");
-	if (c->struct_size < (int32_t)sizeof(mbik_skin_call)) return fail(MBIK_EINVAL, "mbik_skin_call.struct_size is too small");
-	return MBIK_OK;
-}
+inline bool listed(SkinForm form, const mbik_skin_call &c) { return form == kListed || (form == kByCall && c.indices); }
+inline bool compact(const mbik_skin_call &c) { return (c.flags & mbik::kSkinListCompact) != 0; }
 
-// The checks both entries run on a call past its struct's own: the form's existing checks with their texts, then the
-// tangent output's.  0 = run, 1 = nothing to do.
-int check_skin_call(const MeshFacts &f, const mbik_skin_call *c) {
-	if ((c->indices != nullptr) != (c->list_count != nullptr)) return fail(MBIK_EINVAL, "indices and list_count must be given together");
-	if (c->out_tangents && !f.tangents) return fail(MBIK_EINVAL, "out_tangents given for a mesh without tangents");
-	if (c->out_tangents && !c->out_normals) return fail(MBIK_EINVAL, "out_tangents given without out_normals");
-	const bool listed = c->indices != nullptr;
-	int64_t rows = c->count;
-	if (listed) {
-		if (int rc = check_listed(f.B, f.V, f.normals, f.P, c->count, c->indices, c->list_count, c->max_list, c->skin, c->shape_weights,
-					c->flags, c->out_positions, c->out_normals))
-			return rc;
-		rows = (c->flags & mbik::kSkinListCompact) ? c->max_list : c->count;
-	} else {
-		if (c->shape_weights && f.P < 1) return fail(MBIK_EINVAL, "the mesh has no shapes (mbik_mesh_create_shaped)");
-		if (int rc = check_call(f.B, f.V, f.normals, c->count, c->skin, c->out_positions, c->out_normals)) return rc;
-		if (c->shape_weights)
-			if (int rw = check_shape_weights(f.V, f.P, c->count, c->shape_weights, c->out_positions, c->out_normals)) return rw;
+// Every check of a skinning call past the mesh's and the structs' own, in the order the entries have always made them:
+// 0 = run, kNothingToDo, or the refusal.
+int check_skin_call(const MeshFacts &f, const mbik_skin_call &c, SkinForm form) {
+	if (form == kByCall && (c.indices != nullptr) != (c.list_count != nullptr))
+		return fail(MBIK_EINVAL, "indices and list_count must be given together");
+	if (c.out_tangents && !f.tangents) return fail(MBIK_EINVAL, "out_tangents given for a mesh without tangents");
+	if (c.out_tangents && !c.out_normals) return fail(MBIK_EINVAL, "out_tangents given without out_normals");
+	const bool list = listed(form, c);
+	if (list) {
+		// (these two say "unknown flag bits" where check_flags says "unknown flags N", and the listed form has its own words
+		// for a mesh without shapes: both texts are older than the helpers and stay)
+		if (c.flags & ~mbik::kSkinListFlags) return fail(MBIK_EINVAL, "unknown flag bits");
+		if (c.max_list < 0) return fail(MBIK_EINVAL, "negative max_list");
+		if (c.shape_weights && f.P < 1) return fail(MBIK_EINVAL, "shape_weights given for a mesh without shapes");
+	} else if ((c.shape_weights || form == kShaped) && f.P < 1) {
+		return fail(MBIK_EINVAL, "the mesh has no shapes (mbik_mesh_create_shaped)");
 	}
-	if (!c->out_tangents) return 0;
-	const size_t nt = (size_t)rows * f.V * 4 * sizeof(float), nout = (size_t)rows * f.V * 3 * sizeof(float);
-	const auto hit = [&](const void *p, size_t n) { return p && overlap(p, n, c->out_tangents, nt); };
-	if (hit(c->skin, (size_t)c->count * f.B * 12 * sizeof(float))) return fail(MBIK_EINVAL, "out_tangents overlaps skin");
-	if (hit(c->shape_weights, (size_t)c->count * f.P * sizeof(float))) return fail(MBIK_EINVAL, "out_tangents overlaps shape_weights");
-	if (listed && hit(c->indices, (size_t)c->max_list * sizeof(int32_t))) return fail(MBIK_EINVAL, "out_tangents overlaps indices");
-	if (listed && hit(c->list_count, sizeof(int32_t))) return fail(MBIK_EINVAL, "out_tangents overlaps list_count");
-	if (hit(c->out_positions, nout)) return fail(MBIK_EINVAL, "out_tangents overlaps out_positions");
-	if (hit(c->out_normals, nout)) return fail(MBIK_EINVAL, "out_tangents overlaps out_normals");
-	return 0;
+	if (int rc = check_count(c.count)) return rc;
+	if (c.out_normals && !f.normals) return fail(MBIK_EINVAL, "out_normals given for a mesh without normals");
+	if (c.count == 0 || f.V == 0 || (list && c.max_list == 0)) return kNothingToDo;
+	if (int rc = check_given(c.skin, "skin")) return rc;
+	if (int rc = check_given(c.out_positions, "out_positions")) return rc;
+	// the outputs' rows: the listed call's compact form has one a list entry
+	const size_t rows = list && compact(c) ? (size_t)c.max_list : (size_t)c.count, nout = rows * f.V * 3 * sizeof(float);
+	const Range skin{c.skin, (size_t)c.count * f.B * 12 * sizeof(float), "skin"};
+	const Range weights{c.shape_weights, (size_t)c.count * f.P * sizeof(float), "shape_weights"};
+	const Range indices{list ? c.indices : nullptr, (size_t)c.max_list * sizeof(int32_t), "indices"};
+	const Range list_count{list ? c.list_count : nullptr, sizeof(int32_t), "list_count"};
+	const Range out_p{c.out_positions, nout, "out_positions"}, out_n{c.out_normals, nout, "out_normals"};
+	if (int rc = check_disjoint({out_p, out_n}, {skin})) return rc;
+	if (form == kShaped)
+		if (int rc = check_given(c.shape_weights, "shape_weights")) return rc;
+	if (int rc = check_disjoint({out_p, out_n}, {weights})) return rc;
+	if (list) {
+		if (int rc = check_given(c.indices, "indices")) return rc;
+		if (int rc = check_given(c.list_count, "list_count")) return rc;
+		if (int rc = check_disjoint({out_p, out_n}, {indices, list_count})) return rc;
+	}
+	return check_disjoint({Range{c.out_tangents, rows * f.V * 4 * sizeof(float), "out_tangents"}}, {skin, weights, indices, list_count, out_p, out_n});
 }
 
-int check_desc_struct(const mbik_mesh_desc *d) {
-	if (!d) return fail(MBIK_EINVAL, "null desc");
-	if (d->struct_size < (int32_t)sizeof(mbik_mesh_desc)) return fail(MBIK_EINVAL, "mbik_mesh_desc.struct_size is too small");
+// The device tail of every skinning entry: the checks, the launch shape for the call's tiles (skeletons, or list entries),
+// what the mesh knows of the launch, the launch on the mesh's device.
+int skin_on_device(const mbik_mesh *m, const mbik_skin_call &c, SkinForm form, void *hip_stream) {
+	if (int rc = check_given(m, "mesh")) return rc;
+	if (int rc = check_skin_call(MeshFacts{m->B, m->V, m->P, m->normals, m->tangents}, c, form)) return settled(rc);
+	const bool list = listed(form, c);
+	const SkinShape sh = shape_of(m, list ? c.max_list : c.count, c.shape_weights != nullptr);
+	mbik::SkinLaunch a{};
+	a.st = reinterpret_cast<hipStream_t>(hip_stream);
+	a.K = m->K, a.mode = m->mode, a.B = m->B, a.V = m->V, a.P = m->P;
+	a.S = sh.S, a.chunk = sh.chunk, a.chunks = sh.chunks, a.vshift = sh.vshift;
+	a.mesh = m->mesh.as<unsigned char>(), a.mesh_normals = m->normals, a.mesh_tangents = m->tangents;
+	a.count = c.count, a.skin = c.skin, a.shape_weights = c.shape_weights;
+	a.out_p = c.out_positions, a.out_n = c.out_normals, a.out_t = c.out_tangents;
+	if (list) a.indices = c.indices, a.list_count = c.list_count, a.max_list = c.max_list, a.compact = compact(c);
+	return launched(m->device, list ? "listed skinning" : (c.shape_weights ? "shaped skinning" : "skinning"),
+			[&] { return list ? mbik::launch_skin_listed(a) : mbik::launch_skin(a); });
+}
+
+// The host tail of every skinning entry: the description's checks (but the LDS limit: any bone and shape count), the
+// call's, and the host loop of the call's form.
+int skin_on_host(const mbik_mesh_desc &d, const mbik_skin_call &c, SkinForm form) {
+	if (int rc = check_mesh(d.bone_count, d.vertex_count, d.influences, d.positions, d.bone_indices, d.weights)) return rc;
+	if (d.shapes || form == kShaped)
+		if (int rc = check_shapes(d.bone_count, d.vertex_count, d.normals != nullptr, d.shapes, -1)) return rc;
+	if (int rc = check_tangents(d.normals, d.tangents, d.shapes != nullptr, d.shape_tangents)) return rc;
+	const mbik_mesh_shapes none{};
+	const mbik_mesh_shapes &sh = d.shapes ? *d.shapes : none;
+	const int32_t P = sh.shape_count;
+	if (int rc = check_skin_call(MeshFacts{d.bone_count, d.vertex_count, P, d.normals != nullptr, d.tangents != nullptr}, c, form))
+		return settled(rc);
+	const float *tan = c.out_tangents ? d.tangents : nullptr, *stan = c.out_tangents ? d.shape_tangents : nullptr;
+	if (listed(form, c))
+		mbik::skin_vertices_listed_host(d.bone_count, d.vertex_count, d.influences, d.positions, d.normals, d.bone_indices, d.weights, P,
+				sh.mode, sh.positions, sh.normals, c.count, c.indices, c.list_count, c.max_list, c.skin, c.shape_weights, compact(c),
+				c.out_positions, c.out_normals, tan, stan, c.out_tangents);
+	else if (c.shape_weights)
+		mbik::morph_skin_vertices_host(d.bone_count, d.vertex_count, d.influences, d.positions, d.normals, d.bone_indices, d.weights, P,
+				sh.mode, sh.positions, sh.normals, c.count, c.skin, c.shape_weights, c.out_positions, c.out_normals, tan, stan, c.out_tangents);
+	else
+		mbik::skin_vertices_host(d.bone_count, d.vertex_count, d.influences, d.positions, d.normals, d.bone_indices, d.weights, c.count,
+				c.skin, c.out_positions, c.out_normals, tan, c.out_tangents);
 	return MBIK_OK;
+}
+
+// The older entries' arguments as the struct (max_list and flags: the listed form's).
+mbik_skin_call call_of(int32_t count, const float *skin, const float *shape_weights, float *out_positions, float *out_normals,
+		const int32_t *indices = nullptr, const int32_t *list_count = nullptr, int32_t max_list = 0, uint32_t flags = 0) {
+	return mbik_skin_call{(int32_t)sizeof(mbik_skin_call), count, skin, shape_weights, indices, list_count, max_list, flags, out_positions,
+			out_normals, nullptr};
 }
 
 } // namespace
@@ -260,146 +271,78 @@ extern "C" {
 int32_t mbik_mesh_create_desc(const mbik_mesh_desc *d, int32_t device, mbik_mesh **out_mesh) {
 	if (out_mesh) *out_mesh = nullptr;
 	if (int rc = check_desc_struct(d)) return rc;
-	return create_mesh(d->bone_count, d->vertex_count, d->influences, d->positions, d->normals, d->bone_indices, d->weights,
-			d->shapes != nullptr, d->shapes, device, out_mesh, d->tangents, d->shape_tangents);
-}
-
-int32_t mbik_skin_vertices_call(mbik_mesh *m, const mbik_skin_call *c, void *hip_stream) {
-	if (int rc = check_call_struct(c)) return rc;
-	if (!m) return fail(MBIK_EINVAL, "null mesh");
-	const int rc = check_skin_call(MeshFacts{m->B, m->V, m->P, m->normals, m->tangents}, c);
-	if (rc) return rc < 0 ? rc : MBIK_OK;
-	mbik::SkinLaunch a{};
-	a.count = c->count, a.skin = c->skin, a.shape_weights = c->shape_weights;
-	a.out_p = c->out_positions, a.out_n = c->out_normals, a.out_t = c->out_tangents;
-	if (!c->indices)
-		return launch_on_mesh(m, hip_stream, c->count, a, mbik::launch_skin,
-				c->shape_weights ? "shaped skinning launch failed: " : "skinning launch failed: ");
-	a.indices = c->indices, a.list_count = c->list_count, a.max_list = c->max_list, a.compact = (c->flags & mbik::kSkinListCompact) != 0;
-	return launch_on_mesh(m, hip_stream, c->max_list, a, mbik::launch_skin_listed, "listed skinning launch failed: ");
-}
-
-int32_t mbik_skin_vertices_call_cpu(const mbik_mesh_desc *d, const mbik_skin_call *c) {
-	if (int rc = check_desc_struct(d)) return rc;
-	if (int rc = check_call_struct(c)) return rc;
-	if (int rc = check_mesh(d->bone_count, d->vertex_count, d->influences, d->positions, d->bone_indices, d->weights)) return rc;
-	if (d->shapes)
-		if (int rc = check_shapes(d->bone_count, d->vertex_count, d->normals != nullptr, d->shapes, -1)) return rc;
-	if (int rc = check_tangents(d->normals, d->tangents, d->shapes != nullptr, d->shape_tangents)) return rc;
-	const int32_t P = d->shapes ? d->shapes->shape_count : 0;
-	const int rc = check_skin_call(MeshFacts{d->bone_count, d->vertex_count, P, d->normals != nullptr, d->tangents != nullptr}, c);
-	if (rc) return rc < 0 ? rc : MBIK_OK;
-	const float *tan = c->out_tangents ? d->tangents : nullptr, *stan = c->out_tangents ? d->shape_tangents : nullptr;
-	if (c->indices)
-		mbik::skin_vertices_listed_host(d->bone_count, d->vertex_count, d->influences, d->positions, d->normals, d->bone_indices, d->weights,
-				P, d->shapes ? d->shapes->mode : 0, d->shapes ? d->shapes->positions : nullptr, d->shapes ? d->shapes->normals : nullptr,
-				c->count, c->indices, c->list_count, c->max_list, c->skin, c->shape_weights, (c->flags & mbik::kSkinListCompact) != 0,
-				c->out_positions, c->out_normals, tan, stan, c->out_tangents);
-	else if (c->shape_weights)
-		mbik::morph_skin_vertices_host(d->bone_count, d->vertex_count, d->influences, d->positions, d->normals, d->bone_indices, d->weights,
-				P, d->shapes->mode, d->shapes->positions, d->shapes->normals, c->count, c->skin, c->shape_weights, c->out_positions,
-				c->out_normals, tan, stan, c->out_tangents);
-	else
-		mbik::skin_vertices_host(d->bone_count, d->vertex_count, d->influences, d->positions, d->normals, d->bone_indices, d->weights,
-				c->count, c->skin, c->out_positions, c->out_normals, tan, c->out_tangents);
-	return MBIK_OK;
+	return create_mesh(*d, false, device, out_mesh);
 }
 
 int32_t mbik_mesh_create(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions, const float *normals,
 		const int32_t *bone_indices, const float *weights, int32_t device, mbik_mesh **out_mesh) {
-	return create_mesh(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, false, nullptr, device, out_mesh);
+	return create_mesh(desc_of(bone_count, vertex_count, influences, positions, normals, bone_indices, weights), false, device, out_mesh);
 }
 
 int32_t mbik_mesh_create_shaped(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
 		const float *normals, const int32_t *bone_indices, const float *weights, const mbik_mesh_shapes *shapes, int32_t device,
 		mbik_mesh **out_mesh) {
-	return create_mesh(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, true, shapes, device, out_mesh);
+	return create_mesh(desc_of(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, shapes), true, device, out_mesh);
 }
 
 void mbik_mesh_destroy(mbik_mesh *m) { delete m; }
 
 int32_t mbik_mesh_launch_shape(const mbik_mesh *m, int32_t count, int32_t *skeletons_per_block, int32_t *vertex_chunks) {
-	if (!m) return fail(MBIK_EINVAL, "null mesh");
-	if (count < 0) return fail(MBIK_EINVAL, "negative count");
+	if (int rc = check_given(m, "mesh")) return rc;
+	if (int rc = check_count(count)) return rc;
 	const SkinShape sh = shape_of(m, count, m->P > 0);
 	if (skeletons_per_block) *skeletons_per_block = sh.S;
 	if (vertex_chunks) *vertex_chunks = sh.chunks;
 	return MBIK_OK;
 }
 
+int32_t mbik_skin_vertices_call(mbik_mesh *m, const mbik_skin_call *c, void *hip_stream) {
+	if (int rc = check_call_struct(c)) return rc;
+	return skin_on_device(m, *c, kByCall, hip_stream);
+}
+
+int32_t mbik_skin_vertices_call_cpu(const mbik_mesh_desc *d, const mbik_skin_call *c) {
+	if (int rc = check_desc_struct(d)) return rc;
+	if (int rc = check_call_struct(c)) return rc;
+	return skin_on_host(*d, *c, kByCall);
+}
+
 int32_t mbik_skin_vertices(mbik_mesh *m, int32_t count, const float *skin, float *out_positions, float *out_normals,
 		void *hip_stream) {
-	if (!m) return fail(MBIK_EINVAL, "null mesh");
-	const int rc = check_call(m->B, m->V, m->normals, count, skin, out_positions, out_normals);
-	if (rc) return rc < 0 ? rc : MBIK_OK;
-	mbik::SkinLaunch a{};
-	a.count = count, a.skin = skin, a.out_p = out_positions, a.out_n = out_normals;
-	return launch_on_mesh(m, hip_stream, count, a, mbik::launch_skin, "skinning launch failed: ");
+	return skin_on_device(m, call_of(count, skin, nullptr, out_positions, out_normals), kPlain, hip_stream);
 }
 
 int32_t mbik_skin_vertices_shaped(mbik_mesh *m, int32_t count, const float *skin, const float *shape_weights, float *out_positions,
 		float *out_normals, void *hip_stream) {
-	if (!m) return fail(MBIK_EINVAL, "null mesh");
-	if (m->P < 1) return fail(MBIK_EINVAL, "the mesh has no shapes (mbik_mesh_create_shaped)");
-	const int rc = check_call(m->B, m->V, m->normals, count, skin, out_positions, out_normals);
-	if (rc) return rc < 0 ? rc : MBIK_OK;
-	if (int rw = check_shape_weights(m->V, m->P, count, shape_weights, out_positions, out_normals)) return rw;
-	mbik::SkinLaunch a{};
-	a.count = count, a.skin = skin, a.shape_weights = shape_weights, a.out_p = out_positions, a.out_n = out_normals;
-	return launch_on_mesh(m, hip_stream, count, a, mbik::launch_skin, "shaped skinning launch failed: ");
+	return skin_on_device(m, call_of(count, skin, shape_weights, out_positions, out_normals), kShaped, hip_stream);
 }
 
 int32_t mbik_skin_vertices_listed(mbik_mesh *m, int32_t count, const int32_t *indices, const int32_t *list_count, int32_t max_list,
 		const float *skin, const float *shape_weights, uint32_t flags, float *out_positions, float *out_normals, void *hip_stream) {
-	if (!m) return fail(MBIK_EINVAL, "null mesh");
-	const int rc = check_listed(m->B, m->V, m->normals, m->P, count, indices, list_count, max_list, skin, shape_weights, flags,
-			out_positions, out_normals);
-	if (rc) return rc < 0 ? rc : MBIK_OK;
-	mbik::SkinLaunch a{};
-	a.count = count, a.skin = skin, a.shape_weights = shape_weights, a.out_p = out_positions, a.out_n = out_normals;
-	a.indices = indices, a.list_count = list_count, a.max_list = max_list, a.compact = (flags & mbik::kSkinListCompact) != 0;
-	return launch_on_mesh(m, hip_stream, max_list, a, mbik::launch_skin_listed, "listed skinning launch failed: "); // (a tile is S list entries)
+	return skin_on_device(m, call_of(count, skin, shape_weights, out_positions, out_normals, indices, list_count, max_list, flags), kListed,
+			hip_stream);
 }
 
 int32_t mbik_skin_vertices_cpu(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
 		const float *normals, const int32_t *bone_indices, const float *weights, int32_t count, const float *skin,
 		float *out_positions, float *out_normals) {
-	if (int rc = check_mesh(bone_count, vertex_count, influences, positions, bone_indices, weights)) return rc;
-	const int rc = check_call(bone_count, vertex_count, normals != nullptr, count, skin, out_positions, out_normals);
-	if (rc) return rc < 0 ? rc : MBIK_OK;
-	mbik::skin_vertices_host(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, count, skin,
-			out_positions, out_normals);
-	return MBIK_OK;
+	return skin_on_host(desc_of(bone_count, vertex_count, influences, positions, normals, bone_indices, weights),
+			call_of(count, skin, nullptr, out_positions, out_normals), kPlain);
 }
 
 int32_t mbik_skin_vertices_shaped_cpu(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
 		const float *normals, const int32_t *bone_indices, const float *weights, const mbik_mesh_shapes *shapes, int32_t count,
 		const float *skin, const float *shape_weights, float *out_positions, float *out_normals) {
-	if (int rc = check_mesh(bone_count, vertex_count, influences, positions, bone_indices, weights)) return rc;
-	if (int rc = check_shapes(bone_count, vertex_count, normals != nullptr, shapes, -1)) return rc;
-	const int rc = check_call(bone_count, vertex_count, normals != nullptr, count, skin, out_positions, out_normals);
-	if (rc) return rc < 0 ? rc : MBIK_OK;
-	if (int rw = check_shape_weights(vertex_count, shapes->shape_count, count, shape_weights, out_positions, out_normals)) return rw;
-	mbik::morph_skin_vertices_host(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, shapes->shape_count,
-			shapes->mode, shapes->positions, shapes->normals, count, skin, shape_weights, out_positions, out_normals);
-	return MBIK_OK;
+	return skin_on_host(desc_of(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, shapes),
+			call_of(count, skin, shape_weights, out_positions, out_normals), kShaped);
 }
 
 int32_t mbik_skin_vertices_listed_cpu(int32_t bone_count, int32_t vertex_count, int32_t influences, const float *positions,
 		const float *normals, const int32_t *bone_indices, const float *weights, const mbik_mesh_shapes *shapes, int32_t count,
 		const int32_t *indices, const int32_t *list_count, int32_t max_list, const float *skin, const float *shape_weights,
 		uint32_t flags, float *out_positions, float *out_normals) {
-	if (int rc = check_mesh(bone_count, vertex_count, influences, positions, bone_indices, weights)) return rc;
-	if (shapes)
-		if (int rc = check_shapes(bone_count, vertex_count, normals != nullptr, shapes, -1)) return rc;
-	const int32_t P = shapes ? shapes->shape_count : 0;
-	const int rc = check_listed(bone_count, vertex_count, normals != nullptr, P, count, indices, list_count, max_list, skin,
-			shape_weights, flags, out_positions, out_normals);
-	if (rc) return rc < 0 ? rc : MBIK_OK;
-	mbik::skin_vertices_listed_host(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, P,
-			shapes ? shapes->mode : 0, shapes ? shapes->positions : nullptr, shapes ? shapes->normals : nullptr, count, indices,
-			list_count, max_list, skin, shape_weights, (flags & mbik::kSkinListCompact) != 0, out_positions, out_normals);
-	return MBIK_OK;
+	return skin_on_host(desc_of(bone_count, vertex_count, influences, positions, normals, bone_indices, weights, shapes),
+			call_of(count, skin, shape_weights, out_positions, out_normals, indices, list_count, max_list, flags), kListed);
 }
 
 } // extern "C"

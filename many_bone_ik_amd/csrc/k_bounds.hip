@@ -1,4 +1,4 @@
-// mbik_skin_bounds' and mbik_cull_boxes' kernels (bounds.h).
+// mbik_skin_bounds', mbik_cull_boxes' and mbik_cull_lod's kernels (bounds.h, lod.h).
 //
 // Bounds.  A block owns S consecutive skeletons.  Their matrices are one contiguous run of `skin`
 // (S x B x 12 floats) and go into LDS as k_skin.hip's do (lds_copy.h).  Phase 1 is parallel: one
@@ -21,16 +21,35 @@
 // exclusive offsets and writes the total, and mbik_cull_flags_kernel runs again to place the indices
 // (ballot prefix inside a wave, wave counts through LDS, the block's offset from the scan).  Three
 // launches in stream order; no block waits for another inside a launch.
+//
+// LOD lists.  The culling once per range, with the camera and the ranges in the kernel's arguments as
+// well, and the same three launches, since every list needs each of its skeletons' rank:
+//
+//   mbik_lod_select_kernel   runs lod_select, writes state and level and, to the mesh's scratch, one
+//                            member byte a skeleton (bit r: list r names it), and counts each range's
+//                            members in the block into totals[r][block]
+//   mbik_cull_scan_kernel    a block a range: block r turns row r of the totals into exclusive offsets
+//                            and writes list_counts[r]
+//   mbik_lod_place_kernel    reads the member bytes back and places the indices
+//
+// The placement does not run lod_select again: the first kernel has already advanced `state`, so the
+// verdict it would reach is no longer the one the counts were taken from by construction.  The member
+// byte carries the verdict across instead, and the placement reads one byte a skeleton, not a box.
+//
+// The counting and the ranking are wave_vote, block_votes and rank_in_block below.  Every lane of a
+// block meets every ballot and every barrier: the loops over the ranges around them are
+// launch-uniform (range_count is a kernel argument), and so is the scan's loop over n.
 #include <mutex>
 
 #include "bounds.h"
 #include "kernels.h"
 #include "lds_copy.h"
+#include "lod.h"
 
 namespace {
 using namespace mbik;
 
-constexpr int kThreads = 256;
+constexpr int kThreads = 256, kWaves = kThreads / 64;
 
 __global__ __launch_bounds__(kThreads) void mbik_skin_bounds_kernel(int count, int B, int U, int S, const float4 *__restrict__ table,
 		const float *__restrict__ skin, float *__restrict__ boxes) {
@@ -77,9 +96,32 @@ __global__ __launch_bounds__(kThreads) void mbik_skin_bounds_kernel(int count, i
 #endif
 }
 
+// The planes of a call as a kernel argument: read from host memory at the launch, the unused ones zero.
 struct CullPlanes {
 	float4 p[kCullMaxPlanes];
+	CullPlanes(int plane_count, const float *planes) {
+		for (int i = 0; i < kCullMaxPlanes; i++)
+			p[i] = i < plane_count ? make_float4(planes[i * 4], planes[i * 4 + 1], planes[i * 4 + 2], planes[i * 4 + 3]) : make_float4(0, 0, 0, 0);
+	}
 };
+struct LodRanges {
+	float4 r[kLodMaxRanges]; // begin, end, begin_margin, end_margin
+};
+
+// Counting and ranking the lanes of a block that vote in a ballot.  Every lane of the block takes the ballot and calls
+// publish_votes, a barrier follows, then block_votes and rank_in_block read the counts.  lane and wave are the kernel's
+// threadIdx.x & 63 and threadIdx.x >> 6.
+// The wave's first lane writes the ballot's count to *count, the wave's place in the block's counts.
+__device__ inline void publish_votes(unsigned long long ballot, int lane, int *count) {
+	if (lane == 0) *count = __popcll(ballot);
+}
+__device__ inline int block_votes(const int *counts) { return counts[0] + counts[1] + counts[2] + counts[3]; }
+// base + the voting lanes of the block in front of this one: in its wave by the ballot, the waves in front by their counts.
+__device__ inline int rank_in_block(int base, unsigned long long ballot, int lane, int wave, const int *counts) {
+	int at = base + __popcll(ballot & ((1ull << lane) - 1ull));
+	for (int w = 0; w < wave; w++) at += counts[w];
+	return at;
+}
 
 // PLACE false: visible[] (when given) and totals[block] (when given).  PLACE true: totals holds the
 // blocks' exclusive offsets; the visible skeletons' indices go to indices[offset + rank in the block].
@@ -87,7 +129,7 @@ template <bool PLACE>
 __global__ __launch_bounds__(kThreads) void mbik_cull_flags_kernel(int count, const float *__restrict__ boxes,
 		const float *__restrict__ global, float margin, int plane_count, CullPlanes planes, uint8_t *__restrict__ visible,
 		int32_t *__restrict__ totals, int32_t *__restrict__ indices) {
-	__shared__ int wave_count[kThreads / 64];
+	__shared__ int wave_count[kWaves];
 	const int64_t s = (int64_t)blockIdx.x * kThreads + threadIdx.x;
 	bool vis = false;
 	if (s < count)
@@ -102,25 +144,26 @@ __global__ __launch_bounds__(kThreads) void mbik_cull_flags_kernel(int count, co
 	}
 	const unsigned long long ballot = __ballot(vis);
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	if (lane == 0) wave_count[wave] = __popcll(ballot);
+	publish_votes(ballot, lane, &wave_count[wave]);
 	__syncthreads();
 	if constexpr (!PLACE) {
-		if (threadIdx.x == 0) totals[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+		if (threadIdx.x == 0) totals[blockIdx.x] = block_votes(wave_count);
 	} else {
-		int at = totals[blockIdx.x] + __popcll(ballot & ((1ull << lane) - 1ull));
-		for (int w = 0; w < wave; w++) at += wave_count[w];
+		const int at = rank_in_block(totals[blockIdx.x], ballot, lane, wave, wave_count);
 		if (vis) indices[at] = (int32_t)s;
 	}
 }
 
-// One block: totals[0 .. n) become their exclusive prefix sums, visible_count[0] their sum.
-__global__ __launch_bounds__(kThreads) void mbik_cull_scan_kernel(int n, int32_t *__restrict__ totals, int32_t *__restrict__ visible_count) {
-	__shared__ int wave_sum[kThreads / 64];
+// Block r: totals[r][0 .. n) become their exclusive prefix sums, counts[r] their sum.  mbik_cull_boxes has one row and
+// one count; it launches the scan only for a call with a visible_count (indices come with one), so counts is never null.
+__global__ __launch_bounds__(kThreads) void mbik_cull_scan_kernel(int n, int32_t *__restrict__ totals, int32_t *__restrict__ counts) {
+	__shared__ int wave_sum[kWaves];
+	int32_t *row = totals + (size_t)blockIdx.x * n;
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	int carry = 0;
 	for (int base = 0; base < n; base += kThreads) { // (uniform)
 		const int i = base + (int)threadIdx.x;
-		const int v = i < n ? totals[i] : 0;
+		const int v = i < n ? row[i] : 0;
 		int incl = v;
 		for (int d = 1; d < 64; d <<= 1) {
 			const int up = __shfl_up(incl, d, 64);
@@ -130,11 +173,57 @@ __global__ __launch_bounds__(kThreads) void mbik_cull_scan_kernel(int n, int32_t
 		__syncthreads();
 		int before = 0;
 		for (int w = 0; w < wave; w++) before += wave_sum[w];
-		if (i < n) totals[i] = carry + before + incl - v;
-		carry += wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+		if (i < n) row[i] = carry + before + incl - v;
+		carry += block_votes(wave_sum);
 		__syncthreads();
 	}
-	if (threadIdx.x == 0 && visible_count) visible_count[0] = carry;
+	if (threadIdx.x == 0) counts[blockIdx.x] = carry;
+}
+
+__global__ __launch_bounds__(kThreads) void mbik_lod_select_kernel(int count, const float *__restrict__ boxes,
+		const float *__restrict__ global, float margin, int plane_count, CullPlanes planes, float cx, float cy, float cz, int range_count,
+		LodRanges ranges, uint32_t flags, uint8_t *__restrict__ state, uint8_t *__restrict__ level, uint8_t *__restrict__ member,
+		int32_t *__restrict__ totals, int blocks) {
+	__shared__ int wave_count[kLodMaxRanges][kWaves];
+	const int64_t s = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+	LodVerdict v{0, kLodNone, 0};
+	if (s < count) {
+		v = lod_select(
+				box_load(boxes + s * 6), global ? global + s * 12 : nullptr, margin, plane_count,
+				[&](int i, float &nx, float &ny, float &nz, float &d) {
+					const float4 q = planes.p[i];
+					nx = q.x, ny = q.y, nz = q.z, d = q.w;
+				},
+				v3(cx, cy, cz), range_count,
+				[&](int r) {
+					const float4 q = ranges.r[r];
+					return LodRange{q.x, q.y, q.z, q.w};
+				},
+				flags, state[s]);
+		state[s] = v.state;
+		if (level) level[s] = v.level;
+		member[s] = v.member;
+	}
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	for (int r = 0; r < range_count; r++) publish_votes(__ballot((v.member >> r) & 1), lane, &wave_count[r][wave]); // (uniform)
+	__syncthreads();
+	if ((int)threadIdx.x < range_count) totals[(size_t)threadIdx.x * blocks + blockIdx.x] = block_votes(wave_count[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(kThreads) void mbik_lod_place_kernel(int count, int range_count, const uint8_t *__restrict__ member,
+		const int32_t *__restrict__ totals, int blocks, int32_t *__restrict__ indices) {
+	__shared__ int wave_count[kLodMaxRanges][kWaves];
+	const int64_t s = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+	const unsigned m = s < count ? member[s] : 0u;
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	for (int r = 0; r < range_count; r++) publish_votes(__ballot((m >> r) & 1), lane, &wave_count[r][wave]); // (uniform)
+	__syncthreads();
+	for (int r = 0; r < range_count; r++) { // (uniform)
+		const bool in = (m >> r) & 1;
+		const unsigned long long ballot = __ballot(in);
+		const int at = rank_in_block(totals[(size_t)r * blocks + blockIdx.x], ballot, lane, wave, wave_count[r]);
+		if (in) indices[(int64_t)r * count + at] = (int32_t)s;
+	}
 }
 
 } // namespace
@@ -156,9 +245,7 @@ hipError_t launch_skin_bounds(hipStream_t st, int count, int B, int U, int S, co
 
 hipError_t launch_cull(hipStream_t st, int count, const float *boxes, const float *skeleton_global, float margin, int plane_count,
 		const float *planes, uint8_t *visible, int32_t *indices, int32_t *visible_count, int32_t *totals) {
-	CullPlanes cp;
-	for (int i = 0; i < kCullMaxPlanes; i++)
-		cp.p[i] = i < plane_count ? make_float4(planes[i * 4], planes[i * 4 + 1], planes[i * 4 + 2], planes[i * 4 + 3]) : make_float4(0, 0, 0, 0);
+	const CullPlanes cp(plane_count, planes);
 	const int blocks = cull_blocks(count);
 	const bool rank = indices || visible_count;
 	hipLaunchKernelGGL(mbik_cull_flags_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, count, boxes, skeleton_global, margin, plane_count,
@@ -167,6 +254,21 @@ hipError_t launch_cull(hipStream_t st, int count, const float *boxes, const floa
 	if (indices)
 		hipLaunchKernelGGL(mbik_cull_flags_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, count, boxes, skeleton_global, margin,
 				plane_count, cp, (uint8_t *)nullptr, totals, indices);
+	return hipGetLastError();
+}
+
+hipError_t launch_cull_lod(hipStream_t st, int count, const float *boxes, const float *skeleton_global, float margin, int plane_count,
+		const float *planes, const float *camera, int range_count, const LodRange *ranges, uint32_t flags, uint8_t *state, uint8_t *level,
+		int32_t *indices, int32_t *list_counts, int32_t *totals, uint8_t *member) {
+	const CullPlanes cp(plane_count, planes);
+	LodRanges lr;
+	for (int r = 0; r < kLodMaxRanges; r++)
+		lr.r[r] = r < range_count ? make_float4(ranges[r].begin, ranges[r].end, ranges[r].begin_margin, ranges[r].end_margin) : make_float4(0, 0, 0, 0);
+	const int blocks = cull_blocks(count);
+	hipLaunchKernelGGL(mbik_lod_select_kernel, dim3(blocks), dim3(kThreads), 0, st, count, boxes, skeleton_global, margin, plane_count, cp,
+			camera[0], camera[1], camera[2], range_count, lr, flags, state, level, member, totals, blocks);
+	hipLaunchKernelGGL(mbik_cull_scan_kernel, dim3(range_count), dim3(kThreads), 0, st, blocks, totals, list_counts);
+	hipLaunchKernelGGL(mbik_lod_place_kernel, dim3(blocks), dim3(kThreads), 0, st, count, range_count, member, totals, blocks, indices);
 	return hipGetLastError();
 }
 

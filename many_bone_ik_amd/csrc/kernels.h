@@ -203,7 +203,7 @@ hipError_t launch_skin_bounds(hipStream_t st, int count, int B, int U, int S, co
 constexpr int cull_blocks(int count) { return (int)(((int64_t)count + 255) / 256); }
 hipError_t launch_cull(hipStream_t st, int count, const float *boxes, const float *skeleton_global, float margin, int plane_count,
 		const float *planes, uint8_t *visible, int32_t *indices, int32_t *visible_count, int32_t *totals);
-// k_cull_lod.hip: mbik_cull_lod (lod.h).  The same shape once per range: planes, camera and ranges are host memory, copied into
+// k_bounds.hip as well: mbik_cull_lod (lod.h).  The same shape once per range: planes, camera and ranges are host memory, copied into
 // the kernels' arguments; totals is device scratch of range_count * cull_blocks(count) ints and member of count bytes.  Three
 // launches in stream order: state, level, member bytes and block counts; the scan, a row a block; the placement from the bytes.
 struct LodRange;

@@ -1,5 +1,5 @@
 // Distance LOD lists (mbik_cull_lod; include/mbik.h), shared by the device kernels
-// (k_cull_lod.hip) and the host entry (host_lod.cpp).  The semantics are those of Godot 4.3's
+// (k_bounds.hip) and the host entries (host_bounds.cpp).  The semantics are those of Godot 4.3's
 // RendererSceneCull::_visibility_range_check with VISIBILITY_RANGE_FADE_DISABLED, placed in front of
 // mbik_cull_boxes' plane test (bounds.h's cull_visible):
 //

@@ -100,34 +100,54 @@ def _skin_call(count, skin, out_positions, out_normals=None, out_tangents=None, 
                              vp(out_positions), vp(out_normals), vp(out_tangents))
 
 
+def _marshal_mesh(bone_count, positions, bone_indices, weights, normals=None, shape_positions=None, shape_normals=None,
+                  shape_mode="relative", tangents=None, shape_tangents=None):
+    """The mesh arguments every entry takes -> (mbik_mesh_desc, what it points into: keep it alive as long)."""
+    pos, idx, wgt, nrm = _mesh_arrays(positions, bone_indices, weights, normals)
+    shapes, keep = _shape_arrays(pos.shape[0], shape_positions, shape_normals, shape_mode)
+    tan, stan = _tangent_arrays(pos.shape[0], nrm, tangents, shapes, shape_tangents)
+    return _mesh_desc(bone_count, pos, idx, wgt, nrm, tan, shapes, stan), (pos, idx, wgt, nrm, shapes, keep, tan, stan)
+
+
+def _shape_count(desc):
+    return desc.shapes.contents.shape_count if desc.shapes else 0
+
+
+def _out(given, wanted, shape):
+    """An output array of a host call: `given` as it is (float32, `shape`, contiguous; written in place), else NaN-filled when
+    the mesh has the stream (`wanted`), else None."""
+    if given is None:
+        given = np.full(shape, np.nan, np.float32) if wanted else None
+    assert given is None or (given.dtype == np.float32 and given.shape == shape and given.flags.c_contiguous)
+    return given
+
+
+def _skin_inputs(desc, bone_count, skin, shape_weights):
+    """-> (skin [count][bones][12], shape_weights [count][P] or None), contiguous float32."""
+    sk = np.ascontiguousarray(skin, np.float32)
+    assert sk.shape == (sk.shape[0], bone_count, 12), sk.shape
+    cw = None if shape_weights is None else np.ascontiguousarray(shape_weights, np.float32)
+    assert cw is None or not desc.shapes or cw.shape == (sk.shape[0], _shape_count(desc)), cw.shape
+    return sk, cw
+
+
 class Mesh:
-    """One mesh surface on one GPU (mbik_mesh_create).  Immutable; close() frees it."""
+    """One mesh surface on one GPU (mbik_mesh_create_desc).  Immutable; close() frees it."""
 
     def __init__(self, bone_count: int, positions, bone_indices, weights, normals=None, device: int = 0,
                  shape_positions=None, shape_normals=None, shape_mode: str = "relative", tangents=None, shape_tangents=None):
         """shape_positions [P][V][3] (and shape_normals, exactly when `normals` is given) make a
-        shaped mesh (mbik_mesh_create_shaped); shape_mode is 'relative' or 'normalized'.  tangents
-        [V][4] (xyz and the binormal sign; needs normals; with shape_tangents [P][V][3] exactly when
-        the mesh is shaped) make a mesh with tangents (mbik_mesh_create_desc)."""
+        shaped mesh; shape_mode is 'relative' or 'normalized'.  tangents [V][4] (xyz and the binormal
+        sign; needs normals; with shape_tangents [P][V][3] exactly when the mesh is shaped) make a
+        mesh with tangents.  Every form is one mbik_mesh_create_desc."""
         self._L = _lib.load()
-        pos, idx, wgt, nrm = _mesh_arrays(positions, bone_indices, weights, normals)
-        self.bone_count, self.vertex_count, self.influences = int(bone_count), pos.shape[0], idx.shape[1]
-        self.has_normals = nrm is not None
+        desc, _keep = _marshal_mesh(bone_count, positions, bone_indices, weights, normals, shape_positions, shape_normals, shape_mode,
+                                    tangents, shape_tangents)
+        self.bone_count, self.vertex_count, self.influences = int(bone_count), desc.vertex_count, desc.influences
+        self.has_normals, self.has_tangents, self.shape_count = bool(desc.normals), bool(desc.tangents), _shape_count(desc)
         self.device = device
-        shapes, _keep = _shape_arrays(pos.shape[0], shape_positions, shape_normals, shape_mode)
-        self.shape_count = 0 if shapes is None else shapes.shape_count
-        tan, stan = _tangent_arrays(pos.shape[0], nrm, tangents, shapes, shape_tangents)
-        self.has_tangents = tan is not None
         h = C.c_void_p()
-        if tan is not None or stan is not None:
-            desc = _mesh_desc(self.bone_count, pos, idx, wgt, nrm, tan, shapes, stan)
-            check(self._L.mbik_mesh_create_desc(C.byref(desc), device, C.byref(h)))
-        elif shapes is None:
-            check(self._L.mbik_mesh_create(self.bone_count, self.vertex_count, self.influences, _ptr(pos), _ptr(nrm), _ptr(idx),
-                                           _ptr(wgt), device, C.byref(h)))
-        else:
-            check(self._L.mbik_mesh_create_shaped(self.bone_count, self.vertex_count, self.influences, _ptr(pos), _ptr(nrm),
-                                                  _ptr(idx), _ptr(wgt), C.byref(shapes), device, C.byref(h)))
+        check(self._L.mbik_mesh_create_desc(C.byref(desc), device, C.byref(h)))
         self.h = h
 
     def skin_call(self, skin_ptr: int, out_positions_ptr: int, count: int, out_normals_ptr: int = 0, out_tangents_ptr: int = 0,
@@ -142,21 +162,12 @@ class Mesh:
 
     def skin(self, skin_ptr: int, out_positions_ptr: int, count: int, out_normals_ptr: int = 0, stream: int = 0,
              shape_weights_ptr: int = 0, out_tangents_ptr: int = 0) -> None:
-        """mbik_skin_vertices: out_positions [count][vertices][3] (and out_normals) from the device
-        skin transforms [count][bones][12]; asynchronous on `stream`.  With shape_weights_ptr (device,
-        [count][shapes]) mbik_skin_vertices_shaped: each skeleton morphed by its own weights first;
-        without it a shaped mesh skins its base arrays.  With out_tangents_ptr ([count][vertices][4])
-        mbik_skin_vertices_call writes the tangents as well."""
-        if out_tangents_ptr:
-            self.skin_call(skin_ptr, out_positions_ptr, count, out_normals_ptr, out_tangents_ptr, shape_weights_ptr, stream=stream)
-            return
-        if shape_weights_ptr:
-            check(self._L.mbik_skin_vertices_shaped(self.h, count, C.c_void_p(skin_ptr or None), C.c_void_p(shape_weights_ptr),
-                                                    C.c_void_p(out_positions_ptr or None), C.c_void_p(out_normals_ptr or None),
-                                                    C.c_void_p(stream or None)))
-            return
-        check(self._L.mbik_skin_vertices(self.h, count, C.c_void_p(skin_ptr or None), C.c_void_p(out_positions_ptr or None),
-                                         C.c_void_p(out_normals_ptr or None), C.c_void_p(stream or None)))
+        """skin_call()'s plain and shaped forms (what mbik_skin_vertices and mbik_skin_vertices_shaped do):
+        out_positions [count][vertices][3] (and out_normals) from the device skin transforms
+        [count][bones][12]; asynchronous on `stream`.  With shape_weights_ptr (device, [count][shapes])
+        each skeleton is morphed by its own weights first; without it a shaped mesh skins its base
+        arrays.  With out_tangents_ptr ([count][vertices][4]) the tangents are written as well."""
+        self.skin_call(skin_ptr, out_positions_ptr, count, out_normals_ptr, out_tangents_ptr, shape_weights_ptr, stream=stream)
 
     def bone_boxes(self):
         """mbik_mesh_bone_boxes: (boxes [bones][6] position then size, used [bones] uint8); an unused
@@ -208,10 +219,12 @@ class Mesh:
         outside [0, count) is skipped.  In place the outputs are [count][vertices][3] and unlisted rows
         are not touched; compact they are [max_list][vertices][3] and row r belongs to indices[r].
         out_tangents_ptr: the same rows of [vertices][4] (mbik_skin_vertices_call)."""
-        if out_tangents_ptr:
+        if out_tangents_ptr or (indices_ptr and list_count_ptr):
             self.skin_call(skin_ptr, out_positions_ptr, count, out_normals_ptr, out_tangents_ptr, shape_weights_ptr, indices_ptr,
                            list_count_ptr, max_list, compact, stream)
             return
+        # (a call without its list is the struct call's plain form, or refused there in other words: the listed entry says what
+        # it has always said, in the place among its checks where it has always said it)
         check(self._L.mbik_skin_vertices_listed(self.h, count, C.c_void_p(indices_ptr or None), C.c_void_p(list_count_ptr or None),
                                                 count if max_list is None else max_list, C.c_void_p(skin_ptr or None),
                                                 C.c_void_p(shape_weights_ptr or None), _lib.SKIN_LIST_COMPACT if compact else 0,
@@ -250,43 +263,17 @@ def skin_vertices_cpu(bone_count: int, positions, bone_indices, weights, skin, n
     shape_normals) and shape_weights [count][P]: mbik_skin_vertices_shaped_cpu.  With tangents [V][4]
     (and shape_tangents [P][V][3] on a shaped mesh): mbik_skin_vertices_call_cpu, and a third array,
     tangents [count][V][4]."""
-    L = _lib.load()
-    if tangents is not None or shape_tangents is not None:
-        pos, idx, wgt, nrm = _mesh_arrays(positions, bone_indices, weights, normals)
-        sk = np.ascontiguousarray(skin, np.float32)
-        count, V = sk.shape[0], pos.shape[0]
-        assert sk.shape == (count, bone_count, 12), sk.shape
-        shapes, _keep = _shape_arrays(V, shape_positions, shape_normals, shape_mode)
-        tan, stan = _tangent_arrays(V, nrm, tangents, shapes, shape_tangents)
-        cw = None if shape_weights is None else np.ascontiguousarray(shape_weights, np.float32)
-        assert cw is None or shapes is None or cw.shape == (count, shapes.shape_count), cw.shape
-        out_p = np.empty((count, V, 3), np.float32)
-        out_n = None if nrm is None else np.empty((count, V, 3), np.float32)
-        out_t = None if tan is None else np.empty((count, V, 4), np.float32)
-        desc = _mesh_desc(bone_count, pos, idx, wgt, nrm, tan, shapes, stan)
-        call = _skin_call(count, _ptr(sk), _ptr(out_p), _ptr(out_n), _ptr(out_t), _ptr(cw))
-        check(L.mbik_skin_vertices_call_cpu(C.byref(desc), C.byref(call)))
-        return out_p, out_n, out_t
-    pos, idx, wgt, nrm = _mesh_arrays(positions, bone_indices, weights, normals)
-    sk = np.ascontiguousarray(skin, np.float32)
-    count, V = sk.shape[0], pos.shape[0]
-    assert sk.shape == (count, bone_count, 12), sk.shape
-    out_p = np.empty((count, V, 3), np.float32)
-    out_n = None if nrm is None else np.empty((count, V, 3), np.float32)
-    shapes, _keep = _shape_arrays(V, shape_positions, shape_normals, shape_mode)
-    if shapes is not None:
-        if shape_weights is None:
-            raise ValueError("shape_positions without shape_weights")
-        cw = np.ascontiguousarray(shape_weights, np.float32)
-        assert cw.shape == (count, shapes.shape_count), cw.shape
-        check(L.mbik_skin_vertices_shaped_cpu(bone_count, V, idx.shape[1], _ptr(pos), _ptr(nrm), _ptr(idx), _ptr(wgt),
-                                              C.byref(shapes), count, _ptr(sk), _ptr(cw), _ptr(out_p), _ptr(out_n)))
-        return out_p, out_n
-    if shape_weights is not None:
-        raise ValueError("shape_weights without shape_positions")
-    check(L.mbik_skin_vertices_cpu(bone_count, V, idx.shape[1], _ptr(pos), _ptr(nrm), _ptr(idx), _ptr(wgt), count, _ptr(sk),
-                                   _ptr(out_p), _ptr(out_n)))
-    return out_p, out_n
+    desc, _keep = _marshal_mesh(bone_count, positions, bone_indices, weights, normals, shape_positions, shape_normals, shape_mode,
+                                tangents, shape_tangents)
+    with_tangents = tangents is not None or shape_tangents is not None
+    if not with_tangents and bool(desc.shapes) != (shape_weights is not None):
+        raise ValueError("shape_positions without shape_weights" if desc.shapes else "shape_weights without shape_positions")
+    sk, cw = _skin_inputs(desc, bone_count, skin, shape_weights)
+    rows = (sk.shape[0], desc.vertex_count)
+    outs = [_out(None, True, rows + (3,)), _out(None, desc.normals, rows + (3,)), _out(None, desc.tangents, rows + (4,))]
+    call = _skin_call(sk.shape[0], _ptr(sk), *map(_ptr, outs), _ptr(cw))
+    check(_lib.load().mbik_skin_vertices_call_cpu(C.byref(desc), C.byref(call)))
+    return tuple(outs) if with_tangents else tuple(outs[:2])
 
 
 def skin_vertices_listed_cpu(bone_count: int, positions, bone_indices, weights, skin, indices, list_count, max_list=None,
@@ -301,50 +288,29 @@ def skin_vertices_listed_cpu(bone_count: int, positions, bone_indices, weights, 
     shaped bits; shape_positions alone: the base arrays.  With tangents [V][4] (and shape_tangents on a
     shaped mesh): mbik_skin_vertices_call_cpu, and a third array, tangents [rows][V][4] (out_tangents
     as the other two)."""
-    L = _lib.load()
-    pos, idx, wgt, nrm = _mesh_arrays(positions, bone_indices, weights, normals)
-    sk = np.ascontiguousarray(skin, np.float32)
+    desc, _keep = _marshal_mesh(bone_count, positions, bone_indices, weights, normals, shape_positions, shape_normals, shape_mode,
+                                tangents, shape_tangents)
+    with_tangents = tangents is not None or shape_tangents is not None
+    sk, cw = _skin_inputs(desc, bone_count, skin, shape_weights)
     ind = np.ascontiguousarray(indices, np.int32).reshape(-1)
     cnt = np.asarray([int(list_count)], np.int32)
-    count, V = sk.shape[0], pos.shape[0]
     max_list = ind.shape[0] if max_list is None else int(max_list)
-    assert sk.shape == (count, bone_count, 12) and 0 <= max_list <= ind.shape[0], (sk.shape, max_list)
-    rows = max_list if compact else count
-    outs = []
-    for given, wanted in ((out_positions, True), (out_normals, nrm is not None)):
-        if given is None:
-            given = np.full((rows, V, 3), np.nan, np.float32) if wanted else None
-        assert given is None or (given.dtype == np.float32 and given.shape == (rows, V, 3) and given.flags.c_contiguous)
-        outs.append(given)
-    shapes, _keep = _shape_arrays(V, shape_positions, shape_normals, shape_mode)
-    cw = None
-    if shape_weights is not None:
-        cw = np.ascontiguousarray(shape_weights, np.float32)
-        assert shapes is None or cw.shape == (count, shapes.shape_count), cw.shape
-    if tangents is not None or shape_tangents is not None:
-        tan, stan = _tangent_arrays(V, nrm, tangents, shapes, shape_tangents)
-        out_t = out_tangents
-        if out_t is None and tan is not None:
-            out_t = np.full((rows, V, 4), np.nan, np.float32)
-        assert out_t is None or (out_t.dtype == np.float32 and out_t.shape == (rows, V, 4) and out_t.flags.c_contiguous)
-        desc = _mesh_desc(bone_count, pos, idx, wgt, nrm, tan, shapes, stan)
-        call = _skin_call(count, _ptr(sk), _ptr(outs[0]), _ptr(outs[1]), _ptr(out_t), _ptr(cw), _ptr(ind), _ptr(cnt), max_list,
-                          _lib.SKIN_LIST_COMPACT if compact else 0)
-        check(L.mbik_skin_vertices_call_cpu(C.byref(desc), C.byref(call)))
-        return outs[0], outs[1], out_t
-    check(L.mbik_skin_vertices_listed_cpu(bone_count, V, idx.shape[1], _ptr(pos), _ptr(nrm), _ptr(idx), _ptr(wgt),
-                                          None if shapes is None else C.byref(shapes), count, _ptr(ind), _ptr(cnt), max_list, _ptr(sk),
-                                          _ptr(cw), _lib.SKIN_LIST_COMPACT if compact else 0, _ptr(outs[0]), _ptr(outs[1])))
-    return outs[0], outs[1]
+    assert 0 <= max_list <= ind.shape[0], max_list
+    rows = (max_list if compact else sk.shape[0], desc.vertex_count)
+    outs = [_out(out_positions, True, rows + (3,)), _out(out_normals, desc.normals, rows + (3,)),
+            _out(out_tangents, desc.tangents, rows + (4,)) if with_tangents else None]
+    call = _skin_call(sk.shape[0], _ptr(sk), *map(_ptr, outs), _ptr(cw), _ptr(ind), _ptr(cnt), max_list, _lib.SKIN_LIST_COMPACT if compact else 0)
+    check(_lib.load().mbik_skin_vertices_call_cpu(C.byref(desc), C.byref(call)))
+    return tuple(outs) if with_tangents else tuple(outs[:2])
 
 
 def bone_boxes_cpu(bone_count: int, positions, bone_indices, weights):
     """mbik_bone_boxes_cpu (host only): (boxes [bones][6], used [bones] uint8) of a mesh."""
-    L = _lib.load()
-    pos, idx, wgt, _ = _mesh_arrays(positions, bone_indices, weights, None)
+    d, _keep = _marshal_mesh(bone_count, positions, bone_indices, weights)
     boxes = np.zeros((bone_count, 6), np.float32)
     used = np.zeros((bone_count,), np.uint8)
-    check(L.mbik_bone_boxes_cpu(bone_count, pos.shape[0], idx.shape[1], _ptr(pos), _ptr(idx), _ptr(wgt), _ptr(boxes), _ptr(used)))
+    check(_lib.load().mbik_bone_boxes_cpu(bone_count, d.vertex_count, d.influences, d.positions, d.bone_indices, d.weights, _ptr(boxes),
+                                          _ptr(used)))
     return boxes, used
 
 
