@@ -466,14 +466,15 @@ int32_t mbik_pose_blend_cpu(int32_t bone_count, int32_t libm_variant, int32_t co
  *      mbik_pose_blend, not renormalised; key quaternions are used as given.
  *   6. A NaN produced by the arithmetic of 5 is stored as 0x7fc00000; copied bits stay as they are.
  * mbik_clip_sample_cpu gives the same bits from the same code.  Deviations from Godot: _find treats
- * a time within is_equal_approx of a key as that key, here the compare is exact; cubic
- * interpolation, ping-pong, backward playback and key transitions (ease) are not covered.
+ * a time within is_equal_approx of a key as that key, here the compare is exact; ping-pong,
+ * backward playback and key transitions (ease) are not covered.  Cubic interpolation is taken by
+ * sets made with mbik_clipset_create_desc, below (step 5c); this entry refuses it.
  * AnimationMixer's blend of several animations is mbik_clip_sample_layers, below (mbik_pose_blend is
  * the modifier's `influence`, a different function). */
 typedef struct mbik_clip_track {
 	int32_t bone;            /* [0, bone_count) */
 	int32_t channel;         /* 0 position (3 floats a key), 1 rotation (4: x,y,z,w), 2 scale (3) */
-	int32_t interpolation;   /* 0 nearest, 1 linear */
+	int32_t interpolation;   /* 0 nearest, 1 linear; 2 cubic through mbik_clipset_desc only */
 	int32_t loop_wrap;       /* Animation track loop_wrap */
 	int32_t key_count;       /* 0 allowed: same as no track */
 	const double *times;     /* [key_count] seconds, strictly increasing, finite, in [0, length] */
@@ -886,6 +887,114 @@ int32_t mbik_clip_sample_shapes_cpu(int32_t bone_count, const float *rest_pose, 
 int32_t mbik_clip_sample_shapes_layers_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
 		const mbik_clipset_shapes *shapes, int32_t libm_variant, int32_t count, int32_t layer_count, const mbik_clip_layer *layers,
 		uint32_t flags, float *weights_out);
+
+/* Cubic interpolation: Godot's INTERPOLATION_CUBIC (interpolation == 2) on pose tracks and shape
+ * tracks, through every call that reads a clip set.  Purely additive to ABI 15: three new symbols
+ * and two new structs, no existing struct, call, table layout or result bit changed,
+ * MBIK_ABI_VERSION stays 15.  A caller detects the feature by the presence of the symbol
+ * mbik_clipset_create_desc.  The older creation entries and every older _cpu entry keep refusing
+ * interpolation 2 as they did.
+ *
+ * mbik_clipset_create_desc is mbik_clipset_create (shapes NULL) or mbik_clipset_create_shaped, with
+ * the same checks in the same order and the same messages, except that interpolation 2 is taken.
+ * Every other value -- Godot's INTERPOLATION_LINEAR_ANGLE 3 and INTERPOLATION_CUBIC_ANGLE 4 among
+ * them -- stays MBIK_EINVAL "unknown interpolation N", and loop_mode 2 (ping-pong) stays
+ * MBIK_EINVAL.  MBIK_EINVAL before those checks: a null desc, a struct_size below
+ * sizeof(mbik_clipset_desc), flags other than 0.  The device entries -- mbik_clip_sample, _layers,
+ * _shapes, _shapes_layers, mbik_clip_root_motion, _layers, mbik_playback_create -- take such a set
+ * unchanged.  A set without a cubic track, however it was made, runs the same kernels and gives the
+ * same bits as before.
+ *
+ * mbik_clip_call_cpu is the one host-only twin of the six sampling and extraction calls on a set
+ * described by a mbik_clipset_desc, which may hold cubic tracks.  kind selects the call; the fields
+ * it does not name in its older _cpu entry are ignored.  Each kind makes the set's checks (as
+ * mbik_clipset_create_desc; shapes are checked when given, and required by the two SHAPES kinds),
+ * then the call checks of its older _cpu entry with the same messages in the same order, then runs
+ * the same per-item code.  MBIK_EINVAL before those: a null set or call, a struct_size below the
+ * struct's size, set flags other than 0, an unknown kind.
+ *
+ * Semantics -- Godot's core is not part of the reference tree, so mbik_clip_call_cpu is the
+ * specification, modelled on Godot 4.3's Animation::_interpolate, Math::cubic_interpolate_in_time
+ * and Quaternion::spherical_cubic_interpolate_in_time.  mbik_clip_sample's step 5, continued for a
+ * cubic channel: all arithmetic float32 and unfused, in the order written; sums and differences of
+ * times in double, rounded once to float; divisions IEEE; lerp(a, b, w) = a + (b - a) * w.
+ *   5c. i, wrap as in step 5.  The copies are step 5's: n == 1 gives V[0]; not wrap, i < 0 gives
+ *       V[0]; not wrap, i == n-1 gives V[n-1].  (Deviation: Godot evaluates the cubic at c = 0 there,
+ *       the same value but for -0 and non-finite bits.)
+ *       Keys, not wrap (interior i): a = i, b = i+1, pre = max(i-1, 0), post = min(i+2, n-1);
+ *       pre_t = (float)(T[pre] - T[a]), to_t = (float)(T[b] - T[a]), post_t = (float)(T[post] - T[a]).
+ *       Keys, wrap: a = i, or n-1 when i < 0; b = (a+1) mod n, pre = (a-1) mod n, post = (a+2) mod n;
+ *       pre_t = pre > a ? (float)((-length + T[pre]) - T[a]) : (float)(T[pre] - T[a]);
+ *       to_t = b < a ? (float)((length + T[b]) - T[a]) : (float)(T[b] - T[a]);
+ *       post_t = (b < a || post <= a) ? (float)((length + T[post]) - T[a]) : (float)(T[post] - T[a]).
+ *       (At n == 2 and n == 3 pre and post alias a and b, or wrap onto them.)
+ *       c = step 5's weight from / delta with step 5's delta and its three cases (interior,
+ *       i == n-1, i < 0) -- Godot computes to_t and delta separately, and so does this.
+ *       cubic(from, to, pre, post) (Barry-Goldman):
+ *         t  = lerp(0, to_t, c)
+ *         a1 = lerp(pre, from, pre_t == 0 ? 0 : (t - pre_t) / -pre_t)
+ *         a2 = lerp(from, to, to_t == 0 ? 0.5 : t / to_t)
+ *         a3 = lerp(to, post, post_t - to_t == 0 ? 1 : (t - to_t) / (post_t - to_t))
+ *         b1 = lerp(a1, a2, to_t - pre_t == 0 ? 0 : (t - pre_t) / (to_t - pre_t))
+ *         b2 = lerp(a2, a3, post_t == 0 ? 1 : t / post_t)
+ *         result lerp(b1, b2, to_t == 0 ? 0.5 : t / to_t)
+ *       Position, scale and shape values: c == 0 (-0 included; a time exactly on key a, or a
+ *       delta below CMP_EPSILON) gives V[a]'s bits, copied; otherwise cubic(V[a], V[b], V[pre],
+ *       V[post]) per component; step 6.  (Deviation: Godot evaluates the scheme at c == 0 too, whose
+ *       result lerp(pre + (from - pre), from, w) is `from` only when from - pre is a float32 and is
+ *       within an ulp of max(|from - pre|, |from|) of it otherwise.)  The rotation has no such rule.
+ *       Rotation, the key quaternions used as given:
+ *         from, pre, to, post = Basis(q).get_rotation_quaternion() of V[a], V[pre], V[b], V[post];
+ *         pre = signbit(dot(from, pre)) ? -pre : pre;
+ *         flip2 = signbit(dot(from, to)); to = flip2 ? -to : to;
+ *         flip3 = flip2 ? dot(to, post) <= 0 : signbit(dot(to, post)); post = flip3 ? -post : post;
+ *         log(q) = get_axis(q) * angle(q) as (x, y, z, 0), angle(q) = 2 * (w < -1 ? pi : (w > 1 ? 0 :
+ *         acosf(w))) (Math::acos clamps);
+ *         exp(v): theta = length(v), u = normalized(v); identity when theta < CMP_EPSILON or u is not
+ *         normalized (length_squared(u) != 1 and not |length_squared(u) - 1| < 0.001, UNIT_EPSILON);
+ *         otherwise Quaternion(u, theta);
+ *         q1 = from * exp(L1), L1.xyz = cubic(0, log(from^-1 * to), log(from^-1 * pre), log(from^-1 *
+ *         post)) per component; q2 = to * exp(L2), L2.xyz = cubic(log(to^-1 * from), 0, log(to^-1 *
+ *         pre), log(to^-1 * post)); ^-1 is the conjugate;
+ *         result Quaternion::slerp(q1, q2, c) as in mbik_pose_blend, not renormalised; step 6.
+ * Everything else applies to a cubic channel as to a linear one: steps 1 to 4 and 6, the layer rules
+ * of mbik_clip_sample_layers, the seam split of mbik_clip_root_motion (at c == 0 the position, scale
+ * and shape value is V[a] exactly), the shapes' init.  The device gives mbik_clip_call_cpu's
+ * bits.  Not covered: INTERPOLATION_LINEAR_ANGLE / CUBIC_ANGLE, ping-pong, key transitions. */
+typedef struct mbik_clipset_desc {
+	int32_t struct_size;               /* sizeof(mbik_clipset_desc) */
+	int32_t bone_count;
+	const float *rest_pose;            /* [bones][10] */
+	int32_t clip_count;
+	const mbik_clip_desc *clips;       /* a track's interpolation may be 2 */
+	const mbik_clipset_shapes *shapes; /* or NULL: a set without shapes */
+	int32_t libm_variant;
+	uint32_t flags;                    /* 0 */
+} mbik_clipset_desc;
+int32_t mbik_clipset_create_desc(const mbik_clipset_desc *desc, int32_t device, mbik_clipset **out);
+
+#define MBIK_CLIP_CALL_SAMPLE 0              /* mbik_clip_sample_cpu: count, time, clip_index, clip, out (poses) */
+#define MBIK_CLIP_CALL_SAMPLE_LAYERS 1       /* mbik_clip_sample_layers_cpu: count, layer_count, layers, flags, out (poses) */
+#define MBIK_CLIP_CALL_SHAPES 2              /* mbik_clip_sample_shapes_cpu: as SAMPLE, out (weights) */
+#define MBIK_CLIP_CALL_SHAPES_LAYERS 3       /* mbik_clip_sample_shapes_layers_cpu: as SAMPLE_LAYERS, out (weights) */
+#define MBIK_CLIP_CALL_ROOT_MOTION 4         /* mbik_clip_root_motion_cpu: count, root_bone, time_prev, time, clip_index, clip, out (motion), pose */
+#define MBIK_CLIP_CALL_ROOT_MOTION_LAYERS 5  /* mbik_clip_root_motion_layers_cpu: count, layer_count, root_bone, layers, time_prev, flags, out, pose */
+typedef struct mbik_clip_call {
+	int32_t struct_size;           /* sizeof(mbik_clip_call) */
+	int32_t kind;                  /* MBIK_CLIP_CALL_* */
+	int32_t count;
+	int32_t layer_count;
+	int32_t root_bone;
+	int32_t clip;                  /* used when clip_index is NULL */
+	uint32_t flags;
+	const double *time;
+	const double *time_prev;
+	const int32_t *clip_index;
+	const mbik_clip_layer *layers;
+	float *out;                    /* pose_out, weights_out or motion_out */
+	float *pose;                   /* the root-motion kinds: may be NULL */
+} mbik_clip_call;
+int32_t mbik_clip_call_cpu(const mbik_clipset_desc *set, const mbik_clip_call *call);
 
 /* Linear blend skinning of a mesh from skin transforms (ABI 10): what mbik_pose_globals' skinned
  * output exists for, on the device and on the stream of the solve.  The semantics are those of

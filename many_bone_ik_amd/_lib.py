@@ -43,7 +43,8 @@ EXPORTED_SYMBOLS = (
     "mbik_skin_vertices", "mbik_skin_vertices_cpu", "mbik_mesh_launch_shape", "mbik_mesh_create_shaped", "mbik_skin_vertices_shaped",
     "mbik_skin_vertices_shaped_cpu", "mbik_mesh_bone_boxes", "mbik_bone_boxes_cpu", "mbik_skin_bounds", "mbik_skin_bounds_cpu",
     "mbik_cull_boxes", "mbik_cull_boxes_cpu", "mbik_cull_lod", "mbik_cull_lod_cpu", "mbik_skin_vertices_listed", "mbik_skin_vertices_listed_cpu",
-    "mbik_mesh_create_desc", "mbik_skin_vertices_call", "mbik_skin_vertices_call_cpu", "mbik_selftest_math",
+    "mbik_mesh_create_desc", "mbik_skin_vertices_call", "mbik_skin_vertices_call_cpu", "mbik_clipset_create_desc", "mbik_clip_call_cpu",
+    "mbik_selftest_math",
     "mbik_selftest_libm", "mbik_selftest_div", "mbik_selftest_qcp", "mbik_selftest_point_in_limits", "mbik_selftest_xform", "mbik_selftest_topology", "mbik_plan_create_device", "mbik_last_error",
 )
 
@@ -135,6 +136,23 @@ class MbikClipShapeTracks(C.Structure):
 class MbikClipsetShapes(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("shape_count", C.c_int32), ("init", C.c_void_p),
                 ("clips", C.POINTER(MbikClipShapeTracks))]
+
+
+class MbikClipsetDesc(C.Structure):  # mbik_clipset_desc
+    _fields_ = [("struct_size", C.c_int32), ("bone_count", C.c_int32), ("rest_pose", C.c_void_p), ("clip_count", C.c_int32),
+                ("clips", C.POINTER(MbikClipDesc)), ("shapes", C.POINTER(MbikClipsetShapes)), ("libm_variant", C.c_int32),
+                ("flags", C.c_uint32)]
+
+
+class MbikClipCall(C.Structure):  # mbik_clip_call
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("count", C.c_int32), ("layer_count", C.c_int32),
+                ("root_bone", C.c_int32), ("clip", C.c_int32), ("flags", C.c_uint32), ("time", C.c_void_p), ("time_prev", C.c_void_p),
+                ("clip_index", C.c_void_p), ("layers", C.c_void_p), ("out", C.c_void_p), ("pose", C.c_void_p)]
+
+
+# mbik_clip_call.kind
+CLIP_CALL_SAMPLE, CLIP_CALL_SAMPLE_LAYERS, CLIP_CALL_SHAPES, CLIP_CALL_SHAPES_LAYERS, CLIP_CALL_ROOT_MOTION, \
+    CLIP_CALL_ROOT_MOTION_LAYERS = range(6)
 
 
 class MbikMeshShapes(C.Structure):
@@ -404,6 +422,11 @@ def load():
     L.mbik_skin_vertices_call.restype = C.c_int32
     L.mbik_skin_vertices_call_cpu.argtypes = [C.POINTER(MbikMeshDesc), C.POINTER(MbikSkinCall)]
     L.mbik_skin_vertices_call_cpu.restype = C.c_int32
+    if hasattr(L, "mbik_clipset_create_desc"):  # (absent from older A/B builds)
+        L.mbik_clipset_create_desc.argtypes = [C.POINTER(MbikClipsetDesc), C.c_int32, C.POINTER(vp)]
+        L.mbik_clipset_create_desc.restype = C.c_int32
+        L.mbik_clip_call_cpu.argtypes = [C.POINTER(MbikClipsetDesc), C.POINTER(MbikClipCall)]
+        L.mbik_clip_call_cpu.restype = C.c_int32
     L.mbik_last_error.argtypes = []
     L.mbik_last_error.restype = C.c_char_p
     _lib = L

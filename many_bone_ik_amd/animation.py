@@ -33,6 +33,11 @@ animation_set_next.  `Playback.advance()` moves it one frame on and writes the l
 previous times `sample_layers()` and `root_motion_layers()` read, from a device array of commands
 (`pack_commands()`, CMD_DTYPE) or none; `Playback.write()` / `read()` exchange state (SLOT_DTYPE
 records and flag words) with the host.  `playback_advance_cpu()` is the host form.
+
+Cubic interpolation: a track's "interpolation" may be CUBIC in a set made with
+`ClipSet(..., cubic=True)` (mbik_clipset_create_desc) and in the six `*_cpu` functions called with
+`cubic=True` (mbik_clip_call_cpu).  Without `cubic=True` every call is what it was and refuses CUBIC.
+The generators take `interpolations=`, the kinds their tracks draw from.
 """
 from __future__ import annotations
 
@@ -44,7 +49,7 @@ from . import _lib
 from ._lib import check
 
 POSITION, ROTATION, SCALE = 0, 1, 2
-NEAREST, LINEAR = 0, 1
+NEAREST, LINEAR, CUBIC = 0, 1, 2  # CUBIC: only through the `cubic=True` forms (mbik_clipset_create_desc, mbik_clip_call_cpu)
 LOOP_NONE, LOOP_LINEAR = 0, 1
 # floats of a pose record [10] that a channel owns (quaternion xyzw | position | scale)
 CHANNEL_SLICE = {POSITION: slice(4, 7), ROTATION: slice(0, 4), SCALE: slice(7, 10)}
@@ -136,18 +141,48 @@ def _set_args(bone_count, rest_pose, clips, libm_variant, shapes=None):
     return args + [libm_variant], keep + [rest]
 
 
+def _set_desc(bone_count, rest_pose, clips, libm_variant, shapes=None):
+    """(mbik_clipset_desc, the objects its pointers refer to) from _set_args' arguments."""
+    rest = _rest(bone_count, rest_pose)
+    descs, keep = _descs(clips)
+    d = _lib.MbikClipsetDesc()
+    d.struct_size, d.bone_count, d.clip_count, d.libm_variant, d.flags = C.sizeof(_lib.MbikClipsetDesc), int(bone_count), len(clips), libm_variant, 0
+    d.rest_pose = rest.ctypes.data
+    d.clips = C.cast(descs, C.POINTER(_lib.MbikClipDesc))
+    if shapes is not None:
+        sh, keep_sh = _shape_descs(shapes[0], clips, shapes[1])
+        d.shapes = C.pointer(sh)
+        keep += [sh, keep_sh]
+    return d, keep + [rest, descs]
+
+
+def _call_cpu(desc, kind, **fields):
+    """mbik_clip_call_cpu of `kind` on `desc`; fields: mbik_clip_call's, arrays for its pointers."""
+    c = _lib.MbikClipCall()
+    c.struct_size, c.kind = C.sizeof(_lib.MbikClipCall), kind
+    for k, v in fields.items():
+        setattr(c, k, (None if v is None else v.ctypes.data) if k in ("time", "time_prev", "clip_index", "layers", "out", "pose") else v)
+    check(_lib.load().mbik_clip_call_cpu(C.byref(desc), C.byref(c)))
+
+
 class ClipSet:
-    """Several clips of one rig on one GPU (mbik_clipset_create).  Immutable; close() frees it."""
+    """Several clips of one rig on one GPU (mbik_clipset_create).  Immutable; close() frees it.
+    cubic=True: made by mbik_clipset_create_desc, which takes tracks with interpolation CUBIC."""
 
     def __init__(self, bone_count: int, rest_pose, clips, libm_variant: int = 0, device: int = 0, shape_count: int = 0,
-                 shape_init=None):
+                 shape_init=None, cubic: bool = False):
         self._L = _lib.load()
         self.bone_count, self.clip_count, self.libm_variant, self.device = int(bone_count), len(clips), libm_variant, device
         self.shape_count = int(shape_count)
-        args, keep = _set_args(bone_count, rest_pose, clips, libm_variant, (self.shape_count, shape_init) if self.shape_count else None)
+        shapes = (self.shape_count, shape_init) if self.shape_count else None
         h = C.c_void_p()
-        create = self._L.mbik_clipset_create_shaped if self.shape_count else self._L.mbik_clipset_create
-        check(create(*args, device, C.byref(h)))
+        if cubic:
+            desc, keep = _set_desc(bone_count, rest_pose, clips, libm_variant, shapes)
+            check(self._L.mbik_clipset_create_desc(C.byref(desc), device, C.byref(h)))
+        else:
+            args, keep = _set_args(bone_count, rest_pose, clips, libm_variant, shapes)
+            create = self._L.mbik_clipset_create_shaped if self.shape_count else self._L.mbik_clipset_create
+            check(create(*args, device, C.byref(h)))
         del keep
         self.h = h
 
@@ -221,15 +256,20 @@ class ClipSet:
             pass
 
 
-def clip_sample_cpu(bone_count: int, rest_pose, clips, time, clip_index=None, clip: int = 0, libm_variant: int = 0):
+def clip_sample_cpu(bone_count: int, rest_pose, clips, time, clip_index=None, clip: int = 0, libm_variant: int = 0, cubic: bool = False):
     """mbik_clip_sample_cpu (host only): `time` [count] seconds and `clip_index` [count] (or the one
-    `clip`) -> poses [count][bones][10]."""
+    `clip`) -> poses [count][bones][10].  cubic=True (here and in the five functions below): through
+    mbik_clip_call_cpu, which takes tracks with interpolation CUBIC."""
     L = _lib.load()
-    args, keep = _set_args(bone_count, rest_pose, clips, libm_variant)
     t = np.ascontiguousarray(time, np.float64).reshape(-1)
     idx = None if clip_index is None else np.ascontiguousarray(clip_index, np.int32).reshape(-1)
     assert idx is None or idx.shape == t.shape, (idx.shape, t.shape)
     out = np.empty((t.shape[0], bone_count, 10), np.float32)
+    if cubic:
+        desc, keep = _set_desc(bone_count, rest_pose, clips, libm_variant)
+        _call_cpu(desc, _lib.CLIP_CALL_SAMPLE, count=t.shape[0], time=t, clip_index=idx, clip=clip, out=out)
+        return out
+    args, keep = _set_args(bone_count, rest_pose, clips, libm_variant)
     check(L.mbik_clip_sample_cpu(*args, t.shape[0], _ptr(t), _ptr(idx), clip,
                                  _ptr(out)))
     del keep
@@ -250,14 +290,18 @@ def pack_layers(time, clip, weight):
     return out
 
 
-def clip_sample_layers_cpu(bone_count: int, rest_pose, clips, layers, flags: int = 0, libm_variant: int = 0):
+def clip_sample_layers_cpu(bone_count: int, rest_pose, clips, layers, flags: int = 0, libm_variant: int = 0, cubic: bool = False):
     """mbik_clip_sample_layers_cpu (host only): `layers` [count][K] of LAYER_DTYPE (pack_layers) ->
     poses [count][bones][10]."""
     L = _lib.load()
-    args, keep = _set_args(bone_count, rest_pose, clips, libm_variant)
     rec = np.ascontiguousarray(layers, LAYER_DTYPE)
     assert rec.ndim == 2, rec.shape
     out = np.empty((rec.shape[0], bone_count, 10), np.float32)
+    if cubic:
+        desc, keep = _set_desc(bone_count, rest_pose, clips, libm_variant)
+        _call_cpu(desc, _lib.CLIP_CALL_SAMPLE_LAYERS, count=rec.shape[0], layer_count=rec.shape[1], layers=rec, flags=flags, out=out)
+        return out
+    args, keep = _set_args(bone_count, rest_pose, clips, libm_variant)
     check(L.mbik_clip_sample_layers_cpu(*args, rec.shape[0], rec.shape[1], _ptr(rec), flags, _ptr(out)))
     del keep
     return out
@@ -272,7 +316,7 @@ def _pose_arg(pose, count, bone_count):
 
 
 def clip_root_motion_cpu(bone_count: int, rest_pose, clips, time_prev, time, root_bone: int, clip_index=None, clip: int = 0, pose=None,
-                         libm_variant: int = 0):
+                         libm_variant: int = 0, cubic: bool = False):
     """mbik_clip_root_motion_cpu (host only): `time_prev` and `time` [count] seconds and `clip_index`
     [count] (or the one `clip`) -> motion records [count][10].  `pose` (float32 [count][bones][10],
     optional) gets the rest pose's root record in place."""
@@ -283,6 +327,11 @@ def clip_root_motion_cpu(bone_count: int, rest_pose, clips, time_prev, time, roo
     idx = None if clip_index is None else np.ascontiguousarray(clip_index, np.int32).reshape(-1)
     assert t0.shape == t1.shape and (idx is None or idx.shape == t1.shape), (t0.shape, t1.shape)
     out = np.empty((t1.shape[0], 10), np.float32)
+    if cubic:
+        desc, keep_d = _set_desc(bone_count, rest_pose, clips, libm_variant)
+        _call_cpu(desc, _lib.CLIP_CALL_ROOT_MOTION, count=t1.shape[0], root_bone=root_bone, time_prev=t0, time=t1, clip_index=idx, clip=clip,
+                  out=out, pose=_pose_arg(pose, t1.shape[0], bone_count))
+        return out
     check(L.mbik_clip_root_motion_cpu(*args, t1.shape[0], root_bone, _ptr(t0), _ptr(t1), _ptr(idx), clip, _ptr(out),
                                       _ptr(_pose_arg(pose, t1.shape[0], bone_count))))
     del keep
@@ -290,7 +339,7 @@ def clip_root_motion_cpu(bone_count: int, rest_pose, clips, time_prev, time, roo
 
 
 def clip_root_motion_layers_cpu(bone_count: int, rest_pose, clips, layers, time_prev, root_bone: int, flags: int = 0, pose=None,
-                                libm_variant: int = 0):
+                                libm_variant: int = 0, cubic: bool = False):
     """mbik_clip_root_motion_layers_cpu (host only): `layers` [count][K] of LAYER_DTYPE and
     `time_prev` [count][K] seconds -> motion records [count][10]; `pose` as in clip_root_motion_cpu."""
     L = _lib.load()
@@ -299,6 +348,11 @@ def clip_root_motion_layers_cpu(bone_count: int, rest_pose, clips, layers, time_
     assert rec.ndim == 2, rec.shape
     t0 = np.ascontiguousarray(time_prev, np.float64).reshape(rec.shape)
     out = np.empty((rec.shape[0], 10), np.float32)
+    if cubic:
+        desc, keep_d = _set_desc(bone_count, rest_pose, clips, libm_variant)
+        _call_cpu(desc, _lib.CLIP_CALL_ROOT_MOTION_LAYERS, count=rec.shape[0], layer_count=rec.shape[1], root_bone=root_bone, layers=rec,
+                  time_prev=t0, flags=flags, out=out, pose=_pose_arg(pose, rec.shape[0], bone_count))
+        return out
     check(L.mbik_clip_root_motion_layers_cpu(*args, rec.shape[0], rec.shape[1], root_bone, _ptr(rec), _ptr(t0), flags, _ptr(out),
                                              _ptr(_pose_arg(pose, rec.shape[0], bone_count))))
     del keep
@@ -437,7 +491,7 @@ def _shape_only(clips):
                  **{k: c[k] for k in ("shape_tracks", "shape_track_count") if k in c}) for c in clips]
 
 
-def clip_sample_shapes_cpu(shape_count: int, clips, time, clip_index=None, clip: int = 0, shape_init=None):
+def clip_sample_shapes_cpu(shape_count: int, clips, time, clip_index=None, clip: int = 0, shape_init=None, cubic: bool = False):
     """mbik_clip_sample_shapes_cpu (host only): `time` [count] seconds and `clip_index` [count] (or
     the one `clip`) -> weights [count][shape_count]."""
     L = _lib.load()
@@ -446,12 +500,16 @@ def clip_sample_shapes_cpu(shape_count: int, clips, time, clip_index=None, clip:
     idx = None if clip_index is None else np.ascontiguousarray(clip_index, np.int32).reshape(-1)
     assert idx is None or idx.shape == t.shape, (idx.shape, t.shape)
     out = np.empty((t.shape[0], max(int(shape_count), 0)), np.float32)
+    if cubic:
+        desc, keep_d = _set_desc(0, _NO_REST[:0], _shape_only(clips), 0, (shape_count, shape_init))
+        _call_cpu(desc, _lib.CLIP_CALL_SHAPES, count=t.shape[0], time=t, clip_index=idx, clip=clip, out=out)
+        return out
     check(L.mbik_clip_sample_shapes_cpu(*args, t.shape[0], _ptr(t), _ptr(idx), clip, _ptr(out)))
     del keep
     return out
 
 
-def clip_sample_shapes_layers_cpu(shape_count: int, clips, layers, flags: int = 0, shape_init=None):
+def clip_sample_shapes_layers_cpu(shape_count: int, clips, layers, flags: int = 0, shape_init=None, cubic: bool = False):
     """mbik_clip_sample_shapes_layers_cpu (host only): `layers` [count][K] of LAYER_DTYPE
     (pack_layers) -> weights [count][shape_count]."""
     L = _lib.load()
@@ -459,6 +517,10 @@ def clip_sample_shapes_layers_cpu(shape_count: int, clips, layers, flags: int = 
     rec = np.ascontiguousarray(layers, LAYER_DTYPE)
     assert rec.ndim == 2, rec.shape
     out = np.empty((rec.shape[0], max(int(shape_count), 0)), np.float32)
+    if cubic:
+        desc, keep_d = _set_desc(0, _NO_REST[:0], _shape_only(clips), 0, (shape_count, shape_init))
+        _call_cpu(desc, _lib.CLIP_CALL_SHAPES_LAYERS, count=rec.shape[0], layer_count=rec.shape[1], layers=rec, flags=flags, out=out)
+        return out
     check(L.mbik_clip_sample_shapes_layers_cpu(*args, rec.shape[0], rec.shape[1], _ptr(rec), flags, _ptr(out)))
     del keep
     return out
@@ -495,7 +557,14 @@ def _key_rotations(rng, n):
     return q
 
 
-def synthetic_clips(seed: int, bone_count: int, clip_count: int = 3, key_counts=(0, 1, 2, 3, 17), lengths=(1.0, 3.0)):
+def _draw_interpolation(rng, interpolations):
+    """One draw of the stream either way: 0 or 1 as ever, or one of `interpolations`."""
+    if interpolations is None:
+        return int(rng.integers(0, 2))
+    return int(interpolations[rng.integers(0, len(interpolations))])
+
+
+def synthetic_clips(seed: int, bone_count: int, clip_count: int = 3, key_counts=(0, 1, 2, 3, 17), lengths=(1.0, 3.0), interpolations=None):
     """A seeded clip set for a rig of `bone_count` bones: (rest_pose [bones][10], clips).
 
     Every (clip, bone, channel) draws its key count from `key_counts` (0: untracked, no track), its
@@ -503,7 +572,8 @@ def synthetic_clips(seed: int, bone_count: int, clip_count: int = 3, key_counts=
     with LOOP_LINEAR, with lengths drawn from `lengths`.  A third of the tracks keep their keys
     strictly inside (0, length), a third have keys exactly at 0 and at length, and a third a key at
     0 only.  Key rotations are unit quaternions at least 10 degrees apart (the wrap pair included),
-    positions lie in [-1, 1] and scales in [0.5, 1.5]."""
+    positions lie in [-1, 1] and scales in [0.5, 1.5].  interpolations: the kinds a track draws its
+    interpolation from, e.g. (NEAREST, LINEAR, CUBIC); None: NEAREST or LINEAR, the stream as it always was."""
     rng = np.random.default_rng(seed)
     B = int(bone_count)
     rest = np.concatenate([_unit_quats(rng, B), rng.uniform(-1.0, 1.0, (B, 3)), rng.uniform(0.5, 1.5, (B, 3))], axis=1).astype(np.float32)
@@ -514,7 +584,7 @@ def synthetic_clips(seed: int, bone_count: int, clip_count: int = 3, key_counts=
         for bone in range(B):
             for channel in (POSITION, ROTATION, SCALE):
                 n = int(key_counts[rng.integers(0, len(key_counts))])
-                interpolation, loop_wrap, edge = int(rng.integers(0, 2)), int(rng.integers(0, 2)), int(rng.integers(0, 3))
+                interpolation, loop_wrap, edge = _draw_interpolation(rng, interpolations), int(rng.integers(0, 2)), int(rng.integers(0, 3))
                 if n == 0:
                     continue
                 times = np.sort(rng.uniform(0.05 * length, 0.95 * length, n))
@@ -537,7 +607,7 @@ def synthetic_clips(seed: int, bone_count: int, clip_count: int = 3, key_counts=
 
 
 def synthetic_walk_clips(seed: int, bone_count: int, root_bone: int, clip_count: int = 3, key_counts=(0, 1, 2, 3, 17),
-                         lengths=(1.0, 3.0), walk_keys=(2, 3, 9)):
+                         lengths=(1.0, 3.0), walk_keys=(2, 3, 9), interpolations=None):
     """synthetic_clips' set with a walking root: (rest_pose, clips).
 
     The tracks of `root_bone` are replaced, from a random stream of their own (seed + 1): in every
@@ -547,7 +617,7 @@ def synthetic_walk_clips(seed: int, bone_count: int, root_bone: int, clip_count:
     track draws its interpolation and its loop_wrap at random.  The first clip has a scale track of
     the same shape as well.  The last clip leaves the root untracked.  Every other bone is
     synthetic_clips' own."""
-    rest, clips = synthetic_clips(seed, bone_count, clip_count, key_counts, lengths)
+    rest, clips = synthetic_clips(seed, bone_count, clip_count, key_counts, lengths, interpolations)
     rng = np.random.default_rng(seed + 1)
     out = []
     for c, clip in enumerate(clips):
@@ -565,13 +635,13 @@ def synthetic_walk_clips(seed: int, bone_count: int, root_bone: int, clip_count:
                     values = f[:, None] * rng.uniform(-2.0, 2.0, 3)[None, :]
                 else:
                     values = 1.0 + f[:, None] * rng.uniform(-0.25, 0.25, 3)[None, :]
-                tracks.append(dict(bone=int(root_bone), channel=channel, interpolation=int(rng.integers(0, 2)),
+                tracks.append(dict(bone=int(root_bone), channel=channel, interpolation=_draw_interpolation(rng, interpolations),
                                    loop_wrap=int(rng.integers(0, 2)), times=times.astype(np.float64), values=values.astype(np.float32)))
         out.append(dict(clip, tracks=tracks))
     return rest, out
 
 
-def synthetic_shape_tracks(seed: int, shape_count: int, clips, key_counts=(0, 1, 2, 3, 17)):
+def synthetic_shape_tracks(seed: int, shape_count: int, clips, key_counts=(0, 1, 2, 3, 17), interpolations=None):
     """Copies of `clips` with seeded "shape_tracks" for `shape_count` blend shapes added.
 
     synthetic_clips' mix: every (clip, shape) draws its key count from `key_counts` (0: untracked),
@@ -585,7 +655,7 @@ def synthetic_shape_tracks(seed: int, shape_count: int, clips, key_counts=(0, 1,
         tracks = []
         for shape in range(int(shape_count)):
             n = int(key_counts[rng.integers(0, len(key_counts))])
-            interpolation, loop_wrap, edge = int(rng.integers(0, 2)), int(rng.integers(0, 2)), int(rng.integers(0, 3))
+            interpolation, loop_wrap, edge = _draw_interpolation(rng, interpolations), int(rng.integers(0, 2)), int(rng.integers(0, 3))
             if n == 0:
                 continue
             times = np.sort(rng.uniform(0.05 * length, 0.95 * length, n))

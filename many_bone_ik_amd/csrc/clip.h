@@ -1,8 +1,9 @@
 // Animation clip sampling, shared by the device kernel (k_clip.hip) and the host entry
 // mbik_clip_sample_cpu (host_clip.cpp): Godot 4.3's Animation::position_track_interpolate,
 // rotation_track_interpolate and scale_track_interpolate (Animation::_interpolate) for
-// INTERPOLATION_NEAREST / INTERPOLATION_LINEAR, LOOP_NONE / LOOP_LINEAR, forward playback and key
-// transitions of 1, for every bone of a skeleton at that skeleton's time in that skeleton's clip.
+// INTERPOLATION_NEAREST / INTERPOLATION_LINEAR / INTERPOLATION_CUBIC (the samplers' CUBIC forms,
+// DESIGN.md §26), LOOP_NONE / LOOP_LINEAR, forward playback and key transitions of 1, for every
+// bone of a skeleton at that skeleton's time in that skeleton's clip.
 // One code path for both sides, made of IEEE-exact operations only (double compares, differences
 // and sums, an integer fmod, gd_math.h's float arithmetic and blend.h's slerp), so the device and
 // the host produce the same bits.  include/mbik.h (ABI 12) states the semantics; DESIGN.md §16.
@@ -28,6 +29,7 @@ struct ClipHeader {
 };
 constexpr int kClipLinear = 1; // flags: INTERPOLATION_LINEAR (else nearest)
 constexpr int kClipWrap = 2;   //        loop_mode == LOOP_LINEAR && loop_wrap
+constexpr int kClipCubic = 4;  //        INTERPOLATION_CUBIC (never with kClipLinear); sets of mbik_clipset_create_desc only
 struct ClipInfo {
 	double length;
 	int32_t loop_mode, reserved;
@@ -132,6 +134,25 @@ GDI ClipPick clip_pick(const ClipChan &ch) {
 	if (i >= 0 && i < n - 1) return ClipPick{i, i + 1, linear ? kClipInterior : kClipCopy};
 	return ClipPick{n - 1, 0, linear ? (i < 0 ? kClipWrapBefore : kClipWrapAfter) : kClipCopy};
 }
+// The pick of a sampler's CUBIC form (a set that has a cubic track).  A cubic channel's pick that
+// is not one of the copies above also names the keys before a and after b -- clamped into the
+// track, or going round it with wrap -- and says so in `cubic`; every other pick is clip_pick's
+// with pre = a and post = b, so that its two further loads repeat addresses it loads anyway.
+struct ClipPickCubic : ClipPick {
+	int pre, post;
+	bool cubic;
+};
+GDI ClipPickCubic clip_pick_cubic(const ClipChan &ch) {
+	const ClipPick p = clip_pick(ch);
+	const int n = ch.n, i = ch.pos - 1;
+	const bool wrap = (ch.flags & kClipWrap) != 0;
+	const bool copied = n <= 1 || (!wrap && (i < 0 || i == n - 1));
+	if (!(ch.flags & kClipCubic) || copied) return ClipPickCubic{p, p.a, p.b, false};
+	if (!wrap) return ClipPickCubic{ClipPick{i, i + 1, kClipInterior}, i > 0 ? i - 1 : 0, i + 2 < n ? i + 2 : n - 1, true};
+	const int a = i < 0 ? n - 1 : i, b = a + 1 < n ? a + 1 : 0;
+	return ClipPickCubic{ClipPick{a, b, i < 0 ? kClipWrapBefore : (i == n - 1 ? kClipWrapAfter : kClipInterior)}, a > 0 ? a - 1 : n - 1,
+			b + 1 < n ? b + 1 : 0, true};
+}
 // The weight c between the two keys of a pick that is not a copy.  Every difference and sum in
 // double, rounded once to float; the quotient is IEEE float division.
 GDI float clip_weight(int mode, double Ta, double Tb, double tp, double length) {
@@ -160,6 +181,93 @@ GDI V3 clip_value_vec(const ClipPick &p, float c, const ClipValue &a, const Clip
 	if (p.mode == kClipCopy) return v3(a.x, a.y, a.z);
 	const V3 r = v3(a.x, a.y, a.z) + (v3(b.x, b.y, b.z) - v3(a.x, a.y, a.z)) * c; // Vector3::lerp
 	return v3(blend_canon(r.x), blend_canon(r.y), blend_canon(r.z));
+}
+
+// ---- INTERPOLATION_CUBIC (include/mbik.h, the continuation of step 5) ----
+// The times of the keys before a, at b and after b, relative to key a's, as Animation::_interpolate
+// hands them to the *_in_time interpolators: a key that the pick reached by going round the clip
+// counts a length earlier or later.  Sums and differences in double, rounded once.  (A pick that
+// does not wrap has pre <= a < b <= post, so the one form serves both.)
+struct ClipSpan {
+	float pre_t, to_t, post_t;
+};
+GDI ClipSpan clip_span(const ClipPickCubic &p, double Tpre, double Ta, double Tb, double Tpost, double length) {
+	ClipSpan s;
+	s.pre_t = p.pre > p.a ? (float)((-length + Tpre) - Ta) : (float)(Tpre - Ta);
+	s.to_t = p.b < p.a ? (float)((length + Tb) - Ta) : (float)(Tb - Ta);
+	s.post_t = (p.b < p.a || p.post <= p.a) ? (float)((length + Tpost) - Ta) : (float)(Tpost - Ta);
+	return s;
+}
+GDI float clip_lerp(float a, float b, float w) { return a + (b - a) * w; } // Math::lerp
+// Math::cubic_interpolate_in_time (Barry-Goldman): its six lerp weights depend on the times alone,
+// so a channel computes them once for all its components.
+struct ClipCubicW {
+	float a1, a2, a3, b1, b2;
+};
+GDI ClipCubicW clip_cubic_weights(float c, const ClipSpan &s) {
+	const float t = clip_lerp(0.0f, s.to_t, c);
+	ClipCubicW w;
+	w.a1 = s.pre_t == 0.0f ? 0.0f : gd_div(t - s.pre_t, -s.pre_t);
+	w.a2 = s.to_t == 0.0f ? 0.5f : gd_div(t, s.to_t);
+	const float d3 = s.post_t - s.to_t, d1 = s.to_t - s.pre_t;
+	w.a3 = d3 == 0.0f ? 1.0f : gd_div(t - s.to_t, d3);
+	w.b1 = d1 == 0.0f ? 0.0f : gd_div(t - s.pre_t, d1);
+	w.b2 = s.post_t == 0.0f ? 1.0f : gd_div(t, s.post_t);
+	return w;
+}
+GDI float clip_cubic(float from, float to, float pre, float post, const ClipCubicW &w) {
+	const float a1 = clip_lerp(pre, from, w.a1), a2 = clip_lerp(from, to, w.a2), a3 = clip_lerp(to, post, w.a3);
+	const float b1 = clip_lerp(a1, a2, w.b1), b2 = clip_lerp(a2, a3, w.b2);
+	return clip_lerp(b1, b2, w.a2);
+}
+GDI V3 clip_cubic_vec(const ClipValue &a, const ClipValue &b, const ClipValue &pre, const ClipValue &post, const ClipCubicW &w) {
+	return v3(blend_canon(clip_cubic(a.x, b.x, pre.x, post.x, w)), blend_canon(clip_cubic(a.y, b.y, pre.y, post.y, w)),
+			blend_canon(clip_cubic(a.z, b.z, pre.z, post.z, w)));
+}
+// Quaternion::log and Quaternion::exp.
+GDI V3 clip_quat_log(Q q) { return get_axis(q) * get_angle_clamped(q); }
+GDI Q clip_quat_exp(V3 v, int lv) {
+	const float theta = length(v);
+	const V3 u = normalized(v);
+	const float ls = length_sq(u);
+	const bool unit = ls == 1.0f || fabsf(ls - 1.0f) < 0.001f; // Vector3::is_normalized: is_equal_approx(length_squared(), 1, UNIT_EPSILON)
+	if (theta < (float)CMP_EPSILON || !unit) return qid();
+	return axis_angle(u, theta, lv);
+}
+GDI Q clip_quat_neg(Q q) { return q4(-q.x, -q.y, -q.z, -q.w); }
+GDI bool clip_signbit(float x) {
+	union {
+		float f;
+		uint32_t u;
+	} c{x};
+	return (c.u >> 31) != 0;
+}
+// One of the two expmap halves: base * exp(cubic(log(base^-1 * from), log(base^-1 * to), log(base^-1
+// * pre), log(base^-1 * post))), where the log of base^-1 * base is the zero vector as written.
+GDI Q clip_cubic_half(Q base, bool base_is_from, Q other, Q pre, Q post, const ClipCubicW &w, int lv) {
+	const Q inv = inverse(base);
+	const V3 zero = v3(0.0f, 0.0f, 0.0f), lo = clip_quat_log(inv * other);
+	const V3 lf = base_is_from ? zero : lo, lt = base_is_from ? lo : zero;
+	const V3 lp = clip_quat_log(inv * pre), lq = clip_quat_log(inv * post);
+	const V3 ln = v3(clip_cubic(lf.x, lt.x, lp.x, lq.x, w), clip_cubic(lf.y, lt.y, lp.y, lq.y, w), clip_cubic(lf.z, lt.z, lp.z, lq.z, w));
+	return base * clip_quat_exp(ln, lv);
+}
+// Quaternion::spherical_cubic_interpolate_in_time, not renormalised.
+GDI Q clip_cubic_rot(const ClipValue &a, const ClipValue &b, const ClipValue &vpre, const ClipValue &vpost, float c, const ClipCubicW &w,
+		int lv) {
+	const Q from = get_rotation_quaternion(from_quat(q4(a.x, a.y, a.z, a.w)));
+	Q pre = get_rotation_quaternion(from_quat(q4(vpre.x, vpre.y, vpre.z, vpre.w)));
+	Q to = get_rotation_quaternion(from_quat(q4(b.x, b.y, b.z, b.w)));
+	Q post = get_rotation_quaternion(from_quat(q4(vpost.x, vpost.y, vpost.z, vpost.w)));
+	if (clip_signbit(dot(from, pre))) pre = clip_quat_neg(pre);
+	const bool flip2 = clip_signbit(dot(from, to));
+	if (flip2) to = clip_quat_neg(to);
+	const float dp = dot(to, post);
+	if (flip2 ? dp <= 0.0f : clip_signbit(dp)) post = clip_quat_neg(post);
+	const Q q1 = clip_cubic_half(from, true, to, pre, post, w, lv);
+	const Q q2 = clip_cubic_half(to, false, from, pre, post, w, lv);
+	const Q r = blend_slerp(q1, q2, c, lv);
+	return q4(blend_canon(r.x), blend_canon(r.y), blend_canon(r.z), blend_canon(r.w));
 }
 
 // The three channels of one bone at one time in one clip, before they become a pose: steps 2 to 6
@@ -206,6 +314,57 @@ GDI void clip_eval(const ClipLoaded &k, int rot_n, double tp, double length, int
 	out.pos = clip_value_vec(k.pp, pc, k.pVa, k.pVb);
 	out.scl = clip_value_vec(k.ps, sc, k.sVa, k.sVb);
 }
+// The same for a sampler's CUBIC form: four key times and four key values a channel, the keys
+// before a and after b as well -- twenty-four loads, all issued before any is used.
+struct ClipChanKeys {
+	ClipPickCubic p;
+	double Ta, Tb, Tpre, Tpost;
+	ClipValue Va, Vb, Vpre, Vpost;
+};
+struct ClipLoadedCubic {
+	ClipChanKeys pos, rot, scl;
+};
+GDI ClipLoadedCubic clip_load_cubic(const ClipChan &pos, const ClipChan &rot, const ClipChan &scl) {
+	ClipLoadedCubic k;
+	const ClipPickCubic pp = clip_pick_cubic(pos), pr = clip_pick_cubic(rot), ps = clip_pick_cubic(scl);
+	k.pos.p = pp, k.rot.p = pr, k.scl.p = ps;
+	k.pos.Ta = pos.T[pp.a], k.pos.Tb = pos.T[pp.b], k.pos.Tpre = pos.T[pp.pre], k.pos.Tpost = pos.T[pp.post];
+	k.rot.Ta = rot.T[pr.a], k.rot.Tb = rot.T[pr.b], k.rot.Tpre = rot.T[pr.pre], k.rot.Tpost = rot.T[pr.post];
+	k.scl.Ta = scl.T[ps.a], k.scl.Tb = scl.T[ps.b], k.scl.Tpre = scl.T[ps.pre], k.scl.Tpost = scl.T[ps.post];
+	k.pos.Va = pos.V[pp.a], k.pos.Vb = pos.V[pp.b], k.pos.Vpre = pos.V[pp.pre], k.pos.Vpost = pos.V[pp.post];
+	k.rot.Va = rot.V[pr.a], k.rot.Vb = rot.V[pr.b], k.rot.Vpre = rot.V[pr.pre], k.rot.Vpost = rot.V[pr.post];
+	k.scl.Va = scl.V[ps.a], k.scl.Vb = scl.V[ps.b], k.scl.Vpre = scl.V[ps.pre], k.scl.Vpost = scl.V[ps.post];
+	return k;
+}
+// On a key (c == 0, -0 included) the value is V[a]'s bits: the scheme's own result there,
+// lerp(pre + (from - pre), from, w), is `from` only when from - pre is representable.
+GDI V3 clip_value_vec_cubic(const ClipChanKeys &k, float c, double length) {
+	if (!k.p.cubic) return clip_value_vec(k.p, c, k.Va, k.Vb);
+	if (c == 0.0f) return v3(k.Va.x, k.Va.y, k.Va.z);
+	return clip_cubic_vec(k.Va, k.Vb, k.Vpre, k.Vpost, clip_cubic_weights(c, clip_span(k.p, k.Tpre, k.Ta, k.Tb, k.Tpost, length)));
+}
+GDI void clip_eval_cubic(const ClipLoadedCubic &k, int rot_n, double tp, double length, int lv, ClipSampled &out) {
+	const float pc = clip_weight(k.pos.p.mode, k.pos.Ta, k.pos.Tb, tp, length), rc = clip_weight(k.rot.p.mode, k.rot.Ta, k.rot.Tb, tp, length),
+				sc = clip_weight(k.scl.p.mode, k.scl.Ta, k.scl.Tb, tp, length);
+	const ClipChanKeys &r = k.rot;
+	if (rot_n == 0 || r.p.mode == kClipCopy) {
+		out.rot = q4(r.Va.x, r.Va.y, r.Va.z, r.Va.w);
+	} else if (r.p.cubic) {
+		// the spherical cubic, behind a per-lane branch as the slerp is
+		out.rot = clip_cubic_rot(r.Va, r.Vb, r.Vpre, r.Vpost, rc, clip_cubic_weights(rc, clip_span(r.p, r.Tpre, r.Ta, r.Tb, r.Tpost, length)), lv);
+	} else {
+		const Q q = blend_slerp(q4(r.Va.x, r.Va.y, r.Va.z, r.Va.w), q4(r.Vb.x, r.Vb.y, r.Vb.z, r.Vb.w), rc, lv);
+		out.rot = q4(blend_canon(q.x), blend_canon(q.y), blend_canon(q.z), blend_canon(q.w));
+	}
+	out.pos = clip_value_vec_cubic(k.pos, pc, length);
+	out.scl = clip_value_vec_cubic(k.scl, sc, length);
+}
+// One end: the loads and the evaluation of three searched channels, in the sampler's form.
+template <bool CUBIC>
+GDI void clip_load_eval(const ClipChan &pos, const ClipChan &rot, const ClipChan &scl, double tp, double length, int lv, ClipSampled &out) {
+	if constexpr (CUBIC) clip_eval_cubic(clip_load_cubic(pos, rot, scl), rot.n, tp, length, lv, out);
+	else clip_eval(clip_load(pos, rot, scl), rot.n, tp, length, lv, out);
+}
 // hp / hr / hs: the bone's three headers in `info`'s clip, already loaded -- a caller that samples
 // several clips loads the next one's while this one's keys are searched.  What a lane waits for is
 // memory, so the loads are arranged in as few dependent rounds as the data allows: the search
@@ -213,15 +372,17 @@ GDI void clip_eval(const ClipLoaded &k, int rot_n, double tp, double length, int
 // once.  clip_sample_channels_at starts from tp, a finite time step 3 has already mapped into the
 // clip (root_motion.h samples the ends of a frame's segments, the clip's end among them);
 // clip_sample_channels maps the raw time t and calls it.
+template <bool CUBIC = false>
 GDI ClipSampled clip_sample_channels_at(const ClipView &v, const ClipInfo &info, const ClipHeader &hp, const ClipHeader &hr,
 		const ClipHeader &hs, double tp, int lv) {
 	ClipChan pos = clip_chan(v, hp), rot = clip_chan(v, hr), scl = clip_chan(v, hs);
 	ClipSampled out;
 	out.has_pos = pos.n != 0, out.has_rot = rot.n != 0, out.has_scl = scl.n != 0;
 	clip_search(pos, rot, scl, tp);
-	clip_eval(clip_load(pos, rot, scl), rot.n, tp, info.length, lv, out);
+	clip_load_eval<CUBIC>(pos, rot, scl, tp, info.length, lv, out);
 	return out;
 }
+template <bool CUBIC = false>
 GDI ClipSampled clip_sample_channels(const ClipView &v, const ClipInfo &info, const ClipHeader &hp, const ClipHeader &hr,
 		const ClipHeader &hs, double t, int lv) {
 	if (!clip_finite(t)) { // no key is read
@@ -231,11 +392,12 @@ GDI ClipSampled clip_sample_channels(const ClipView &v, const ClipInfo &info, co
 		out.rot = q4(nan, nan, nan, nan), out.pos = v3(nan, nan, nan), out.scl = v3(nan, nan, nan);
 		return out;
 	}
-	return clip_sample_channels_at(v, info, hp, hr, hs, clip_time(t, info.length, info.loop_mode), lv);
+	return clip_sample_channels_at<CUBIC>(v, info, hp, hr, hs, clip_time(t, info.length, info.loop_mode), lv);
 }
 
 // One bone of one skeleton: out10 = the pose (quaternion xyzw, position, scale) of `bone` at raw
 // time t in clip `clip`: the sampled channels, and the rest pose's bits where a channel has no keys.
+template <bool CUBIC = false>
 GDI void clip_sample_bone(const ClipView &v, int clip, int bone, double t, int lv, float *out10) {
 	if (clip < 0 || clip >= v.clip_count) {
 		for (int f = 0; f < 10; f++) out10[f] = clip_nan();
@@ -244,7 +406,7 @@ GDI void clip_sample_bone(const ClipView &v, int clip, int bone, double t, int l
 	const ClipInfo info = v.clips[clip];
 	const ClipHeader *h = v.headers + ((int64_t)clip * v.B + bone) * 3;
 	const float *rest = v.rest + (int64_t)bone * 10;
-	const ClipSampled s = clip_sample_channels(v, info, h[0], h[1], h[2], t, lv);
+	const ClipSampled s = clip_sample_channels<CUBIC>(v, info, h[0], h[1], h[2], t, lv);
 	out10[0] = s.has_rot ? s.rot.x : rest[0], out10[1] = s.has_rot ? s.rot.y : rest[1];
 	out10[2] = s.has_rot ? s.rot.z : rest[2], out10[3] = s.has_rot ? s.rot.w : rest[3];
 	out10[4] = s.has_pos ? s.pos.x : rest[4], out10[5] = s.has_pos ? s.pos.y : rest[5], out10[6] = s.has_pos ? s.pos.z : rest[6];

@@ -60,6 +60,7 @@ GDI bool clip_layer_blend(bool normalize, int key_count, float w, float total, f
 // K x 3 key counts; then the accumulation, which loads layer l + 1's record and headers before
 // layer l's keys are searched, so that a lane has two layers' loads in flight.  A layer whose
 // three channels are all off, untracked or skipped by weight reads no key.
+template <bool CUBIC = false>
 GDI void clip_layers_bone(const ClipView &v, const ClipLayer *L, int K, uint32_t flags, int bone, int lv, float *out10) {
 	for (int l = 0; l < K; l++) {
 		const int c = L[l].clip;
@@ -112,7 +113,7 @@ GDI void clip_layers_bone(const ClipView &v, const ClipLayer *L, int K, uint32_t
 		if (!do_pos) h.pos = none;
 		if (!do_rot) h.rot = none;
 		if (!do_scl) h.scl = none;
-		const ClipSampled x = clip_sample_channels(v, info, h.pos, h.rot, h.scl, rec.time, lv);
+		const ClipSampled x = clip_sample_channels<CUBIC>(v, info, h.pos, h.rot, h.scl, rec.time, lv);
 		if (do_pos) pos = pos + (x.pos - Ip) * bp, any_pos = true;
 		if (do_scl) scl = scl + (x.scl - Is) * bs, any_scl = true;
 		if (do_rot) {

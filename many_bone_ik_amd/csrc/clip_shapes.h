@@ -26,7 +26,7 @@ struct ShapeKey {
 };
 static_assert(sizeof(ShapeKey) == 16, "a shape key is 16 bytes");
 struct ShapeHeader {
-	int32_t key_off, key_count, flags, reserved; // flags: kClipLinear, kClipWrap
+	int32_t key_off, key_count, flags, reserved; // flags: kClipLinear, kClipWrap, kClipCubic
 };
 struct ShapeView {
 	int32_t P, clip_count;
@@ -39,6 +39,9 @@ struct ShapeView {
 // A tracked shape (h.key_count != 0) at raw time t in the clip `info`: mbik_clip_sample's steps 2,
 // 3, 5 and 6 on one float.  The dependent rounds of loads: the search, one 8-byte load a step;
 // then the two key records, 16 bytes each, which bring both times and both values.
+// CUBIC (a set with a cubic shape track): four key records, the ones before a and after b as well,
+// all loaded before any is used; a pick that is not cubic repeats a's and b's addresses.
+template <bool CUBIC = false>
 GDI float shape_sample_keys(const ShapeView &v, const ClipInfo &info, const ShapeHeader &h, double t) {
 	if (!clip_finite(t)) return clip_nan(); // no key is read
 	const double tp = clip_time(t, info.length, info.loop_mode);
@@ -52,6 +55,17 @@ GDI float shape_sample_keys(const ShapeView &v, const ClipInfo &info, const Shap
 		const double tk = keys[in ? k : 0].time;
 		pos += in && tk <= tp ? step : 0;
 	}
+	if constexpr (CUBIC) {
+		const ClipPickCubic p = clip_pick_cubic(ClipChan{nullptr, nullptr, n, h.flags, pos});
+		const ShapeKey a = keys[p.a], b = keys[p.b], pre = keys[p.pre], post = keys[p.post];
+		if (p.mode == kClipCopy) return a.value;
+		const float c = clip_weight(p.mode, a.time, b.time, tp, info.length);
+		if (!p.cubic) return blend_canon(a.value + (b.value - a.value) * c);
+		if (c == 0.0f) return a.value; // on a key: the key's bits (clip.h clip_value_vec_cubic)
+		// Math::cubic_interpolate_in_time
+		const ClipCubicW w = clip_cubic_weights(c, clip_span(p, pre.time, a.time, b.time, post.time, info.length));
+		return blend_canon(clip_cubic(a.value, b.value, pre.value, post.value, w));
+	}
 	const ClipPick p = clip_pick(ClipChan{nullptr, nullptr, n, h.flags, pos});
 	const ShapeKey a = keys[p.a], b = keys[p.b];
 	if (p.mode == kClipCopy) return a.value;
@@ -60,12 +74,13 @@ GDI float shape_sample_keys(const ShapeView &v, const ClipInfo &info, const Shap
 }
 
 // mbik_clip_sample_shapes for one (skeleton, shape).
+template <bool CUBIC = false>
 GDI float shape_sample(const ShapeView &v, int clip, int shape, double t) {
 	if (clip < 0 || clip >= v.clip_count) return clip_nan();
 	const ClipInfo info = v.clips[clip];
 	const ShapeHeader h = v.headers[(int64_t)clip * v.P + shape];
 	if (h.key_count == 0) return v.init[shape];
-	return shape_sample_keys(v, info, h, t);
+	return shape_sample_keys<CUBIC>(v, info, h, t);
 }
 
 GDI ShapeHeader shape_layer_header(const ShapeView &v, int clip, int shape) {
@@ -78,6 +93,7 @@ GDI ShapeHeader shape_layer_header(const ShapeView &v, int clip, int shape) {
 // array of per-layer values): validity from the records alone, before any table is touched; in
 // normalize mode the shape's total; then the accumulation, which loads layer l + 1's record, clip
 // info and header before layer l's keys are searched.
+template <bool CUBIC = false>
 GDI float shape_layers(const ShapeView &v, const ClipLayer *L, int K, uint32_t flags, int shape) {
 	for (int l = 0; l < K; l++) {
 		const int c = L[l].clip;
@@ -110,7 +126,7 @@ GDI float shape_layers(const ShapeView &v, const ClipLayer *L, int K, uint32_t f
 		}
 		float blend;
 		if (!clip_layer_blend(normalize, h.key_count, clip_layer_weight(rec.weight), total, blend)) continue; // no key load
-		const float x = shape_sample_keys(v, info, h, rec.time);
+		const float x = shape_sample_keys<CUBIC>(v, info, h, rec.time);
 		acc = acc + (x - I) * blend, any = true;
 	}
 	return any ? blend_canon(acc) : I;

@@ -590,6 +590,10 @@ GDI V3 get_axis(Q q) {
 	return v3(q.x * r, q.y * r, q.z * r);
 }
 GDI float get_angle(Q q) { return 2 * acos_f(q.w); }
+// Quaternion::get_angle through Godot's Math::acos, which clamps its argument: pi below -1, 0 above
+// 1 (a NaN passes both compares).  The clip samplers' Quaternion::log takes this form, where a key
+// quaternion is used as given; the solve's quaternions are unit and keep the form above.
+GDI float get_angle_clamped(Q q) { return 2 * (q.w < -1.0f ? (float)PI : (q.w > 1.0f ? 0.0f : acos_f(q.w))); }
 
 // ---------------- Basis ----------------
 GDI B3 bset(float xx, float xy, float xz, float yx, float yy, float yz, float zx, float zy, float zz) {

@@ -13,6 +13,7 @@
 
 #include <cmath>
 #include <cstddef>
+#include <type_traits>
 
 #include "clip_shapes.h"
 #include "root_motion.h"
@@ -25,6 +26,7 @@ struct mbik_clipset {
 	DevBuf blob;
 	mbik::ClipView view{}; // device pointers into blob
 	int32_t P = 0;         // 0: a set without shapes
+	bool cubic_pose = false, cubic_shapes = false; // a pose / shape header carries kClipCubic: the kernels' CUBIC forms
 	DevBuf shape_blob;
 	mbik::ShapeView shapes{}; // device pointers into shape_blob
 };
@@ -34,11 +36,11 @@ namespace {
 // A key track's checks past the place it names (bone and channel, or shape), and its header: what the pose tracks and the
 // shape tracks share.  0: `h` is filled and the caller appends the key_count keys at key_total; kNothingToDo: a track without
 // keys, the same as no track; < 0: a refusal.  `values` is tested for null only; duplicate() is the text behind `tw` for a
-// header that already has keys.
+// header that already has keys.  allow_cubic: interpolation 2 is taken (mbik_clipset_create_desc, mbik_clip_call_cpu).
 template <class Header, class Duplicate>
-int pack_track(int32_t interpolation, int32_t loop_wrap, int32_t key_count, const double *times, const void *values, const mbik_clip_desc &d,
+int pack_track(bool allow_cubic, int32_t interpolation, int32_t loop_wrap, int32_t key_count, const double *times, const void *values, const mbik_clip_desc &d,
 		const std::string &tw, size_t key_total, const char *too_many_keys, Header &h, Duplicate duplicate) {
-	if (interpolation != 0 && interpolation != 1) return fail(MBIK_EINVAL, tw + ": unknown interpolation " + std::to_string(interpolation));
+	if (interpolation != 0 && interpolation != 1 && !(allow_cubic && interpolation == 2)) return fail(MBIK_EINVAL, tw + ": unknown interpolation " + std::to_string(interpolation));
 	if (key_count < 0) return fail(MBIK_EINVAL, tw + ": negative key_count");
 	if (key_count == 0) return kNothingToDo;
 	if (!times || !values) return fail(MBIK_EINVAL, tw + ": null times or values");
@@ -51,7 +53,7 @@ int pack_track(int32_t interpolation, int32_t loop_wrap, int32_t key_count, cons
 		if (i > 0 && !(x > times[i - 1])) return fail(MBIK_EINVAL, tw + ": key times are not strictly increasing at key " + std::to_string(i));
 	}
 	h.key_off = (int32_t)key_total, h.key_count = key_count;
-	h.flags = (interpolation == 1 ? mbik::kClipLinear : 0) | (d.loop_mode == 1 && loop_wrap ? mbik::kClipWrap : 0);
+	h.flags = (interpolation == 1 ? mbik::kClipLinear : 0) | (interpolation == 2 ? mbik::kClipCubic : 0) | (d.loop_mode == 1 && loop_wrap ? mbik::kClipWrap : 0);
 	return 0;
 }
 
@@ -68,11 +70,16 @@ struct PackedSet {
 	std::vector<mbik::ShapeHeader> shape_headers;
 	std::vector<mbik::ShapeKey> keys;
 	std::vector<float> init;
+	bool cubic_pose = false, cubic_shapes = false; // a pose / shape track with keys is cubic
+	int32_t libm = 0;
 
 	// The pose tracks, then with `shaped` the shape tracks: mbik_clipset_create[_shaped]'s refusals in their order.
+	// allow_cubic: the entries that take a mbik_clipset_desc.
 	int pack(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *descs, int32_t libm_variant, bool shaped,
-			const mbik_clipset_shapes *sh) {
+			const mbik_clipset_shapes *sh, bool allow_cubic = false) {
+		cubic = allow_cubic;
 		if (int rc = pack_pose(bone_count, rest_pose, clip_count, descs, libm_variant)) return rc;
+		libm = libm_variant;
 		return shaped ? pack_shapes(descs, sh) : MBIK_OK;
 	}
 	mbik::ClipView view() const {
@@ -83,6 +90,8 @@ struct PackedSet {
 	}
 
 private:
+	bool cubic = false; // pack()'s allow_cubic
+
 	int pack_pose(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *descs, int32_t libm_variant) {
 		if (bone_count < 0 || clip_count < 0) return fail(MBIK_EINVAL, "negative count");
 		if (!rest_pose) return fail(MBIK_EINVAL, "null rest_pose");
@@ -106,12 +115,13 @@ private:
 				const std::string tw = where + " track " + std::to_string(k);
 				if (t.bone < 0 || t.bone >= B) return fail(MBIK_EINVAL, tw + ": bone " + std::to_string(t.bone) + " outside [0, " + std::to_string(B) + ")");
 				if (t.channel < 0 || t.channel > 2) return fail(MBIK_EINVAL, tw + ": unknown channel " + std::to_string(t.channel));
-				const int rc = pack_track(t.interpolation, t.loop_wrap, t.key_count, t.times, t.values, d, tw, times.size(),
+				const int rc = pack_track(cubic, t.interpolation, t.loop_wrap, t.key_count, t.times, t.values, d, tw, times.size(),
 						"more than 2^31 keys in a clip set", headers[((size_t)c * B + t.bone) * 3 + t.channel], [&] {
 							return ": a second track with keys for bone " + std::to_string(t.bone) + " channel " + std::to_string(t.channel);
 						});
 				if (rc < 0) return rc;
 				if (rc == kNothingToDo) continue;
+				cubic_pose = cubic_pose || t.interpolation == 2;
 				const int w = t.channel == 1 ? 4 : 3;
 				for (int32_t i = 0; i < t.key_count; i++) {
 					const float *v = t.values + (size_t)i * w;
@@ -146,11 +156,12 @@ private:
 				const mbik_shape_track &t = st.tracks[k];
 				const std::string tw = where + " shape track " + std::to_string(k);
 				if (t.shape < 0 || t.shape >= P) return fail(MBIK_EINVAL, tw + ": shape " + std::to_string(t.shape) + " outside [0, " + std::to_string(P) + ")");
-				const int rc = pack_track(t.interpolation, t.loop_wrap, t.key_count, t.times, t.values, descs[c], tw, keys.size(),
+				const int rc = pack_track(cubic, t.interpolation, t.loop_wrap, t.key_count, t.times, t.values, descs[c], tw, keys.size(),
 						"more than 2^31 shape keys in a clip set", shape_headers[(size_t)c * P + t.shape],
 						[&] { return ": a second track with keys for shape " + std::to_string(t.shape); });
 				if (rc < 0) return rc;
 				if (rc == kNothingToDo) continue;
+				cubic_shapes = cubic_shapes || t.interpolation == 2;
 				for (int32_t i = 0; i < t.key_count; i++) keys.push_back(mbik::ShapeKey{t.times[i], t.values[i], 0.0f});
 			}
 		}
@@ -269,30 +280,99 @@ int check_root_apply(int32_t count, const float *motion, uint32_t flags, const f
 }
 static_assert(MBIK_ROOT_MOTION_ORTHONORMALIZE == mbik::kRootMotionOrthonormalize, "the flag is root_motion.h's");
 
-// The host form of both extraction calls: one skeleton after the other through root_motion.h.
-void root_motion_host(const mbik::ClipView &v, int32_t libm, int32_t count, int32_t K, int32_t root, const mbik::ClipLayer *L,
-		const double *time_prev, const double *time, const int32_t *clip_index, int32_t clip, uint32_t flags, float *motion_out, float *pose) {
-	for (int64_t s = 0; s < count; s++) {
-		float *pose_s = pose ? pose + s * v.B * 10 : nullptr;
-		if (L) {
-			mbik::root_motion_skeleton(v, mbik::RootLayers{L + s * K, time_prev + s * K}, K, flags, root, libm, motion_out + s * 10, pose_s);
-		} else {
-			const mbik::RootPlain src{mbik::ClipLayer{time[s], clip_index ? clip_index[s] : clip, 1.0f}, time_prev[s]};
-			mbik::root_motion_skeleton(v, src, 1, 0u, root, libm, motion_out + s * 10, pose_s);
-		}
-	}
+const mbik::ClipLayer *records(const mbik_clip_layer *layers) { return reinterpret_cast<const mbik::ClipLayer *>(layers); }
+
+// The per-item code's CUBIC form for a set that has a cubic track, its plain form otherwise: f(std::bool_constant<CUBIC>).
+template <class F>
+void with_cubic(bool cubic, F f) {
+	if (cubic) f(std::true_type{});
+	else f(std::false_type{});
 }
 
-// mbik_clipset_create, and with `shaped` mbik_clipset_create_shaped.
+// The host forms' loops over a packed and checked set: one item after the other through the code the kernels run.
+void sample_host(const PackedSet &pk, int32_t count, const double *time, const int32_t *clip_index, int32_t clip, float *pose_out) {
+	const mbik::ClipView v = pk.view();
+	with_cubic(pk.cubic_pose, [&](auto cubic) {
+		for (int64_t s = 0; s < count; s++) {
+			const int32_t c = clip_index ? clip_index[s] : clip;
+			for (int32_t b = 0; b < v.B; b++) mbik::clip_sample_bone<decltype(cubic)::value>(v, c, b, time[s], pk.libm, pose_out + (s * v.B + b) * 10);
+		}
+	});
+}
+
+void sample_layers_host(const PackedSet &pk, int32_t count, int32_t K, const mbik_clip_layer *layers, uint32_t flags, float *pose_out) {
+	const mbik::ClipView v = pk.view();
+	with_cubic(pk.cubic_pose, [&](auto cubic) {
+		for (int64_t s = 0; s < count; s++)
+			for (int32_t b = 0; b < v.B; b++)
+				mbik::clip_layers_bone<decltype(cubic)::value>(v, records(layers) + s * K, K, flags, b, pk.libm, pose_out + (s * v.B + b) * 10);
+	});
+}
+
+void sample_shapes_host(const PackedSet &pk, int32_t count, const double *time, const int32_t *clip_index, int32_t clip, float *weights_out) {
+	const mbik::ShapeView v = pk.shape_view();
+	with_cubic(pk.cubic_shapes, [&](auto cubic) {
+		for (int64_t s = 0; s < count; s++)
+			for (int32_t j = 0; j < v.P; j++)
+				weights_out[s * v.P + j] = mbik::shape_sample<decltype(cubic)::value>(v, clip_index ? clip_index[s] : clip, j, time[s]);
+	});
+}
+
+void sample_shapes_layers_host(const PackedSet &pk, int32_t count, int32_t K, const mbik_clip_layer *layers, uint32_t flags,
+		float *weights_out) {
+	const mbik::ShapeView v = pk.shape_view();
+	with_cubic(pk.cubic_shapes, [&](auto cubic) {
+		for (int64_t s = 0; s < count; s++)
+			for (int32_t j = 0; j < v.P; j++)
+				weights_out[s * v.P + j] = mbik::shape_layers<decltype(cubic)::value>(v, records(layers) + s * K, K, flags, j);
+	});
+}
+
+// The host form of both extraction calls: one skeleton after the other through root_motion.h.
+void root_motion_host(const PackedSet &pk, int32_t count, int32_t K, int32_t root, const mbik::ClipLayer *L, const double *time_prev,
+		const double *time, const int32_t *clip_index, int32_t clip, uint32_t flags, float *motion_out, float *pose) {
+	const mbik::ClipView v = pk.view();
+	with_cubic(pk.cubic_pose, [&](auto cubic) {
+		constexpr bool CUBIC = decltype(cubic)::value;
+		for (int64_t s = 0; s < count; s++) {
+			float *pose_s = pose ? pose + s * v.B * 10 : nullptr;
+			if (L) {
+				mbik::root_motion_skeleton<CUBIC>(v, mbik::RootLayers{L + s * K, time_prev + s * K}, K, flags, root, pk.libm, motion_out + s * 10,
+						pose_s);
+			} else {
+				const mbik::RootPlain src{mbik::ClipLayer{time[s], clip_index ? clip_index[s] : clip, 1.0f}, time_prev[s]};
+				mbik::root_motion_skeleton<CUBIC>(v, src, 1, 0u, root, pk.libm, motion_out + s * 10, pose_s);
+			}
+		}
+	});
+}
+
+// The struct checks of the entries that take a mbik_clipset_desc or a mbik_clip_call.
+int check_set_desc(const mbik_clipset_desc *d) {
+	if (!d) return fail(MBIK_EINVAL, "null mbik_clipset_desc");
+	if (d->struct_size < (int32_t)sizeof(mbik_clipset_desc)) return fail(MBIK_EINVAL, "mbik_clipset_desc.struct_size is too small");
+	if (d->flags != 0) return fail(MBIK_EINVAL, "mbik_clipset_desc.flags must be 0");
+	return MBIK_OK;
+}
+int check_call_struct(const mbik_clip_call *c) {
+	if (!c) return fail(MBIK_EINVAL, "null mbik_clip_call");
+	if (c->struct_size < (int32_t)sizeof(mbik_clip_call)) return fail(MBIK_EINVAL, "mbik_clip_call.struct_size is too small");
+	if (c->kind < MBIK_CLIP_CALL_SAMPLE || c->kind > MBIK_CLIP_CALL_ROOT_MOTION_LAYERS)
+		return fail(MBIK_EINVAL, "unknown mbik_clip_call.kind " + std::to_string(c->kind));
+	return MBIK_OK;
+}
+
+// mbik_clipset_create, with `shaped` mbik_clipset_create_shaped, and with allow_cubic mbik_clipset_create_desc.
 int create_set(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips, bool shaped,
-		const mbik_clipset_shapes *shapes, int32_t libm_variant, int32_t device, mbik_clipset **out) {
+		const mbik_clipset_shapes *shapes, int32_t libm_variant, int32_t device, mbik_clipset **out, bool allow_cubic = false) {
 	if (!out) return fail(MBIK_EINVAL, "null out");
 	*out = nullptr;
 	PackedSet pk;
-	if (int rc = pk.pack(bone_count, rest_pose, clip_count, clips, libm_variant, shaped, shapes)) return rc;
+	if (int rc = pk.pack(bone_count, rest_pose, clip_count, clips, libm_variant, shaped, shapes, allow_cubic)) return rc;
 	if (int rc = check_device(device)) return rc;
 	std::unique_ptr<mbik_clipset> s(new mbik_clipset());
 	s->device = device, s->B = bone_count, s->clip_count = clip_count, s->libm = libm_variant;
+	s->cubic_pose = pk.cubic_pose, s->cubic_shapes = pk.cubic_shapes;
 	DeviceGuard guard(device);
 	Blob b;
 	const size_t o_info = b.add(pk.clips), o_head = b.add(pk.headers), o_time = b.add(pk.times), o_val = b.add(pk.values), o_rest = b.add(pk.rest);
@@ -320,7 +400,6 @@ int check_set(const mbik_clipset *s, bool shapes = false) {
 }
 
 hipStream_t stream_of(void *hip_stream) { return reinterpret_cast<hipStream_t>(hip_stream); }
-const mbik::ClipLayer *records(const mbik_clip_layer *layers) { return reinterpret_cast<const mbik::ClipLayer *>(layers); }
 
 } // namespace
 
@@ -357,6 +436,12 @@ int32_t mbik_clipset_create_shaped(int32_t bone_count, const float *rest_pose, i
 	return create_set(bone_count, rest_pose, clip_count, clips, true, shapes, libm_variant, device, out);
 }
 
+int32_t mbik_clipset_create_desc(const mbik_clipset_desc *d, int32_t device, mbik_clipset **out) {
+	if (out) *out = nullptr;
+	if (int rc = check_set_desc(d)) return rc;
+	return create_set(d->bone_count, d->rest_pose, d->clip_count, d->clips, d->shapes != nullptr, d->shapes, d->libm_variant, device, out, true);
+}
+
 void mbik_clipset_destroy(mbik_clipset *s) { delete s; }
 
 int32_t mbik_clip_sample(mbik_clipset *s, int32_t count, const double *time, const int32_t *clip_index, int32_t clip, float *pose_out,
@@ -365,7 +450,7 @@ int32_t mbik_clip_sample(mbik_clipset *s, int32_t count, const double *time, con
 	if (int rc = check_sample(s->B, s->clip_count, count, time, clip_index, clip, pose_out)) return settled(rc);
 	if (int rc = check_total(count, s->B, "bones")) return rc;
 	return launched(s->device, "clip sample",
-			[&] { return mbik::launch_clip(stream_of(hip_stream), s->view, s->libm, (int64_t)count * s->B, time, clip_index, clip, pose_out); });
+			[&] { return mbik::launch_clip(stream_of(hip_stream), s->view, s->libm, s->cubic_pose, (int64_t)count * s->B, time, clip_index, clip, pose_out); });
 }
 
 int32_t mbik_clip_sample_cpu(int32_t bone_count, const float *rest_pose, int32_t clip_count, const mbik_clip_desc *clips,
@@ -373,11 +458,7 @@ int32_t mbik_clip_sample_cpu(int32_t bone_count, const float *rest_pose, int32_t
 	PackedSet pk;
 	if (int rc = pk.pack(bone_count, rest_pose, clip_count, clips, libm_variant, false, nullptr)) return rc;
 	if (int rc = check_sample(bone_count, clip_count, count, time, clip_index, clip, pose_out)) return settled(rc);
-	const mbik::ClipView v = pk.view();
-	for (int64_t s = 0; s < count; s++) {
-		const int32_t c = clip_index ? clip_index[s] : clip;
-		for (int32_t b = 0; b < bone_count; b++) mbik::clip_sample_bone(v, c, b, time[s], libm_variant, pose_out + (s * bone_count + b) * 10);
-	}
+	sample_host(pk, count, time, clip_index, clip, pose_out);
 	return MBIK_OK;
 }
 
@@ -387,7 +468,7 @@ int32_t mbik_clip_sample_layers(mbik_clipset *s, int32_t count, int32_t layer_co
 	if (int rc = check_sample_layers((int64_t)s->B * 10, count, layer_count, layers, flags, pose_out, "pose_out")) return settled(rc);
 	if (int rc = check_total(count, s->B, "bones")) return rc;
 	return launched(s->device, "layered clip sample", [&] {
-		return mbik::launch_clip_layers(stream_of(hip_stream), s->view, s->libm, (int64_t)count * s->B, records(layers), layer_count, flags, pose_out);
+		return mbik::launch_clip_layers(stream_of(hip_stream), s->view, s->libm, s->cubic_pose, (int64_t)count * s->B, records(layers), layer_count, flags, pose_out);
 	});
 }
 
@@ -396,10 +477,7 @@ int32_t mbik_clip_sample_layers_cpu(int32_t bone_count, const float *rest_pose, 
 	PackedSet pk;
 	if (int rc = pk.pack(bone_count, rest_pose, clip_count, clips, libm_variant, false, nullptr)) return rc;
 	if (int rc = check_sample_layers((int64_t)bone_count * 10, count, layer_count, layers, flags, pose_out, "pose_out")) return settled(rc);
-	const mbik::ClipView v = pk.view();
-	for (int64_t s = 0; s < count; s++)
-		for (int32_t b = 0; b < bone_count; b++)
-			mbik::clip_layers_bone(v, records(layers) + s * layer_count, layer_count, flags, b, libm_variant, pose_out + (s * bone_count + b) * 10);
+	sample_layers_host(pk, count, layer_count, layers, flags, pose_out);
 	return MBIK_OK;
 }
 
@@ -409,7 +487,7 @@ int32_t mbik_clip_sample_shapes(mbik_clipset *s, int32_t count, const double *ti
 	if (int rc = check_sample_shapes(s->P, s->clip_count, count, time, clip_index, clip, weights_out)) return settled(rc);
 	if (int rc = check_total(count, s->P, "weights")) return rc;
 	return launched(s->device, "shape sample", [&] {
-		return mbik::launch_clip_shapes(stream_of(hip_stream), s->shapes, (int64_t)count * s->P, time, clip_index, clip, weights_out);
+		return mbik::launch_clip_shapes(stream_of(hip_stream), s->shapes, s->cubic_shapes, (int64_t)count * s->P, time, clip_index, clip, weights_out);
 	});
 }
 
@@ -419,7 +497,7 @@ int32_t mbik_clip_sample_shapes_layers(mbik_clipset *s, int32_t count, int32_t l
 	if (int rc = check_sample_layers(s->P, count, layer_count, layers, flags, weights_out, "weights_out")) return settled(rc);
 	if (int rc = check_total(count, s->P, "weights")) return rc;
 	return launched(s->device, "layered shape sample", [&] {
-		return mbik::launch_clip_shapes_layers(stream_of(hip_stream), s->shapes, (int64_t)count * s->P, records(layers), layer_count, flags,
+		return mbik::launch_clip_shapes_layers(stream_of(hip_stream), s->shapes, s->cubic_shapes, (int64_t)count * s->P, records(layers), layer_count, flags,
 				weights_out);
 	});
 }
@@ -429,10 +507,8 @@ int32_t mbik_clip_sample_shapes_cpu(int32_t bone_count, const float *rest_pose, 
 		float *weights_out) {
 	PackedSet pk;
 	if (int rc = pk.pack(bone_count, rest_pose, clip_count, clips, libm_variant, true, shapes)) return rc;
-	const mbik::ShapeView v = pk.shape_view();
-	if (int rc = check_sample_shapes(v.P, clip_count, count, time, clip_index, clip, weights_out)) return settled(rc);
-	for (int64_t s = 0; s < count; s++)
-		for (int32_t j = 0; j < v.P; j++) weights_out[s * v.P + j] = mbik::shape_sample(v, clip_index ? clip_index[s] : clip, j, time[s]);
+	if (int rc = check_sample_shapes((int32_t)pk.init.size(), clip_count, count, time, clip_index, clip, weights_out)) return settled(rc);
+	sample_shapes_host(pk, count, time, clip_index, clip, weights_out);
 	return MBIK_OK;
 }
 
@@ -441,10 +517,8 @@ int32_t mbik_clip_sample_shapes_layers_cpu(int32_t bone_count, const float *rest
 		uint32_t flags, float *weights_out) {
 	PackedSet pk;
 	if (int rc = pk.pack(bone_count, rest_pose, clip_count, clips, libm_variant, true, shapes)) return rc;
-	const mbik::ShapeView v = pk.shape_view();
-	if (int rc = check_sample_layers(v.P, count, layer_count, layers, flags, weights_out, "weights_out")) return settled(rc);
-	for (int64_t s = 0; s < count; s++)
-		for (int32_t j = 0; j < v.P; j++) weights_out[s * v.P + j] = mbik::shape_layers(v, records(layers) + s * layer_count, layer_count, flags, j);
+	if (int rc = check_sample_layers((int64_t)pk.init.size(), count, layer_count, layers, flags, weights_out, "weights_out")) return settled(rc);
+	sample_shapes_layers_host(pk, count, layer_count, layers, flags, weights_out);
 	return MBIK_OK;
 }
 
@@ -453,7 +527,7 @@ int32_t mbik_clip_root_motion(mbik_clipset *s, int32_t count, int32_t root_bone,
 	if (int rc = check_set(s)) return rc;
 	if (int rc = check_root_motion(s->B, s->clip_count, count, root_bone, time_prev, time, clip_index, clip, motion_out, pose)) return settled(rc);
 	return launched(s->device, "root motion", [&] {
-		return mbik::launch_root_motion(stream_of(hip_stream), s->view, s->libm, count, 1, root_bone, nullptr, time_prev, time, clip_index, clip, 0u,
+		return mbik::launch_root_motion(stream_of(hip_stream), s->view, s->libm, s->cubic_pose, count, 1, root_bone, nullptr, time_prev, time, clip_index, clip, 0u,
 				motion_out, pose);
 	});
 }
@@ -463,7 +537,7 @@ int32_t mbik_clip_root_motion_layers(mbik_clipset *s, int32_t count, int32_t lay
 	if (int rc = check_set(s)) return rc;
 	if (int rc = check_root_motion_layers(s->B, count, layer_count, root_bone, layers, time_prev, flags, motion_out, pose)) return settled(rc);
 	return launched(s->device, "layered root motion", [&] {
-		return mbik::launch_root_motion(stream_of(hip_stream), s->view, s->libm, count, layer_count, root_bone, records(layers), time_prev, nullptr,
+		return mbik::launch_root_motion(stream_of(hip_stream), s->view, s->libm, s->cubic_pose, count, layer_count, root_bone, records(layers), time_prev, nullptr,
 				nullptr, 0, flags, motion_out, pose);
 	});
 }
@@ -481,7 +555,7 @@ int32_t mbik_clip_root_motion_cpu(int32_t bone_count, const float *rest_pose, in
 	PackedSet pk;
 	if (int rc = pk.pack(bone_count, rest_pose, clip_count, clips, libm_variant, false, nullptr)) return rc;
 	if (int rc = check_root_motion(bone_count, clip_count, count, root_bone, time_prev, time, clip_index, clip, motion_out, pose)) return settled(rc);
-	root_motion_host(pk.view(), libm_variant, count, 1, root_bone, nullptr, time_prev, time, clip_index, clip, 0u, motion_out, pose);
+	root_motion_host(pk, count, 1, root_bone, nullptr, time_prev, time, clip_index, clip, 0u, motion_out, pose);
 	return MBIK_OK;
 }
 
@@ -491,8 +565,46 @@ int32_t mbik_clip_root_motion_layers_cpu(int32_t bone_count, const float *rest_p
 	PackedSet pk;
 	if (int rc = pk.pack(bone_count, rest_pose, clip_count, clips, libm_variant, false, nullptr)) return rc;
 	if (int rc = check_root_motion_layers(bone_count, count, layer_count, root_bone, layers, time_prev, flags, motion_out, pose)) return settled(rc);
-	root_motion_host(pk.view(), libm_variant, count, layer_count, root_bone, records(layers), time_prev, nullptr, nullptr, 0, flags, motion_out, pose);
+	root_motion_host(pk, count, layer_count, root_bone, records(layers), time_prev, nullptr, nullptr, 0, flags, motion_out, pose);
 	return MBIK_OK;
+}
+
+int32_t mbik_clip_call_cpu(const mbik_clipset_desc *d, const mbik_clip_call *c) {
+	if (int rc = check_set_desc(d)) return rc;
+	if (int rc = check_call_struct(c)) return rc;
+	const bool shape_kind = c->kind == MBIK_CLIP_CALL_SHAPES || c->kind == MBIK_CLIP_CALL_SHAPES_LAYERS;
+	PackedSet pk;
+	if (int rc = pk.pack(d->bone_count, d->rest_pose, d->clip_count, d->clips, d->libm_variant, shape_kind || d->shapes != nullptr, d->shapes, true))
+		return rc;
+	const int32_t B = d->bone_count, P = (int32_t)pk.init.size();
+	switch (c->kind) {
+	case MBIK_CLIP_CALL_SAMPLE:
+		if (int rc = check_sample(B, d->clip_count, c->count, c->time, c->clip_index, c->clip, c->out)) return settled(rc);
+		sample_host(pk, c->count, c->time, c->clip_index, c->clip, c->out);
+		return MBIK_OK;
+	case MBIK_CLIP_CALL_SAMPLE_LAYERS:
+		if (int rc = check_sample_layers((int64_t)B * 10, c->count, c->layer_count, c->layers, c->flags, c->out, "pose_out")) return settled(rc);
+		sample_layers_host(pk, c->count, c->layer_count, c->layers, c->flags, c->out);
+		return MBIK_OK;
+	case MBIK_CLIP_CALL_SHAPES:
+		if (int rc = check_sample_shapes(P, d->clip_count, c->count, c->time, c->clip_index, c->clip, c->out)) return settled(rc);
+		sample_shapes_host(pk, c->count, c->time, c->clip_index, c->clip, c->out);
+		return MBIK_OK;
+	case MBIK_CLIP_CALL_SHAPES_LAYERS:
+		if (int rc = check_sample_layers(P, c->count, c->layer_count, c->layers, c->flags, c->out, "weights_out")) return settled(rc);
+		sample_shapes_layers_host(pk, c->count, c->layer_count, c->layers, c->flags, c->out);
+		return MBIK_OK;
+	case MBIK_CLIP_CALL_ROOT_MOTION:
+		if (int rc = check_root_motion(B, d->clip_count, c->count, c->root_bone, c->time_prev, c->time, c->clip_index, c->clip, c->out, c->pose))
+			return settled(rc);
+		root_motion_host(pk, c->count, 1, c->root_bone, nullptr, c->time_prev, c->time, c->clip_index, c->clip, 0u, c->out, c->pose);
+		return MBIK_OK;
+	default: // MBIK_CLIP_CALL_ROOT_MOTION_LAYERS
+		if (int rc = check_root_motion_layers(B, c->count, c->layer_count, c->root_bone, c->layers, c->time_prev, c->flags, c->out, c->pose))
+			return settled(rc);
+		root_motion_host(pk, c->count, c->layer_count, c->root_bone, records(c->layers), c->time_prev, nullptr, nullptr, 0, c->flags, c->out, c->pose);
+		return MBIK_OK;
+	}
 }
 
 int32_t mbik_root_motion_apply_cpu(int32_t count, const float *motion, uint32_t flags, float *skeleton_global) {

@@ -58,36 +58,40 @@ __device__ __forceinline__ void clip_frame(int B, int64_t total, float *pose_out
 }
 
 // LV: the set's libm_variant (gd::LIBM_FMA / LIBM_SSE2), a compile-time constant of sin_f.
-template <int LV>
+// CUBIC: the set has a cubic pose track (clip.h); a set without runs the <LV, false>
+// kernels, which are what they were before cubic tracks existed.
+template <int LV, bool CUBIC>
 __global__ __launch_bounds__(kClipThreads) void mbik_clip_kernel(ClipView v, int64_t total, const double *time, const int32_t *clip_index,
 		int clip, float *pose_out) {
 	clip_frame(v.B, total, pose_out,
-			[&](int64_t s, int bone, float *out) { clip_sample_bone(v, clip_index ? clip_index[s] : clip, bone, time[s], LV, out); });
+			[&](int64_t s, int bone, float *out) { clip_sample_bone<CUBIC>(v, clip_index ? clip_index[s] : clip, bone, time[s], LV, out); });
 }
 
 // (An occupancy target of 4 waves a SIMD holds the allocation at 128 VGPRs without a spill, and
 // measured the same time as the 136-140 VGPRs and 3 waves the compiler picks on its own: §20.)
-template <int LV>
+template <int LV, bool CUBIC>
 __global__ __launch_bounds__(kClipThreads) void mbik_clip_layers_kernel(ClipView v, int64_t total, const ClipLayer *layers, int K,
 		uint32_t flags, float *pose_out) {
-	clip_frame(v.B, total, pose_out, [&](int64_t s, int bone, float *out) { clip_layers_bone(v, layers + s * K, K, flags, bone, LV, out); });
+	clip_frame(v.B, total, pose_out, [&](int64_t s, int bone, float *out) { clip_layers_bone<CUBIC>(v, layers + s * K, K, flags, bone, LV, out); });
 }
 } // namespace
 
 namespace mbik {
 
-hipError_t launch_clip(hipStream_t st, const ClipView &v, int libm, int64_t total_bones, const double *time, const int32_t *clip_index,
+hipError_t launch_clip(hipStream_t st, const ClipView &v, int libm, bool cubic, int64_t total_bones, const double *time, const int32_t *clip_index,
 		int clip, float *pose_out) {
 	const unsigned blocks = (unsigned)((total_bones + kClipThreads - 1) / kClipThreads);
-	const auto kernel = libm == LIBM_SSE2 ? mbik_clip_kernel<LIBM_SSE2> : mbik_clip_kernel<LIBM_FMA>;
+	const auto kernel = cubic ? (libm == LIBM_SSE2 ? mbik_clip_kernel<LIBM_SSE2, true> : mbik_clip_kernel<LIBM_FMA, true>)
+							  : (libm == LIBM_SSE2 ? mbik_clip_kernel<LIBM_SSE2, false> : mbik_clip_kernel<LIBM_FMA, false>);
 	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kClipThreads), 0, st, v, total_bones, time, clip_index, clip, pose_out);
 	return hipGetLastError();
 }
 
-hipError_t launch_clip_layers(hipStream_t st, const ClipView &v, int libm, int64_t total_bones, const ClipLayer *layers, int layer_count,
+hipError_t launch_clip_layers(hipStream_t st, const ClipView &v, int libm, bool cubic, int64_t total_bones, const ClipLayer *layers, int layer_count,
 		uint32_t flags, float *pose_out) {
 	const unsigned blocks = (unsigned)((total_bones + kClipThreads - 1) / kClipThreads);
-	const auto kernel = libm == LIBM_SSE2 ? mbik_clip_layers_kernel<LIBM_SSE2> : mbik_clip_layers_kernel<LIBM_FMA>;
+	const auto kernel = cubic ? (libm == LIBM_SSE2 ? mbik_clip_layers_kernel<LIBM_SSE2, true> : mbik_clip_layers_kernel<LIBM_FMA, true>)
+							  : (libm == LIBM_SSE2 ? mbik_clip_layers_kernel<LIBM_SSE2, false> : mbik_clip_layers_kernel<LIBM_FMA, false>);
 	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kClipThreads), 0, st, v, total_bones, layers, layer_count, flags, pose_out);
 	return hipGetLastError();
 }

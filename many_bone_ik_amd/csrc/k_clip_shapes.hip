@@ -24,39 +24,43 @@ using namespace mbik;
 
 constexpr int kShapeThreads = 256;
 
+// CUBIC: the set has a cubic shape track (clip_shapes.h); a set without runs the
+// <false> kernels, which are what they were before cubic tracks existed.
+template <bool CUBIC>
 __global__ __launch_bounds__(kShapeThreads) void mbik_clip_shapes_kernel(ShapeView v, int64_t total, const double *time,
 		const int32_t *clip_index, int clip, float *weights_out) {
 	const int64_t b0 = (int64_t)blockIdx.x * kShapeThreads;
 	const int t = threadIdx.x;
 	if (b0 + t >= total) return;
 	const BatchLane ln = batch_lane(v.P, b0, t);
-	weights_out[b0 + t] = shape_sample(v, clip_index ? clip_index[ln.s] : clip, ln.item, time[ln.s]);
+	weights_out[b0 + t] = shape_sample<CUBIC>(v, clip_index ? clip_index[ln.s] : clip, ln.item, time[ln.s]);
 }
 
+template <bool CUBIC>
 __global__ __launch_bounds__(kShapeThreads) void mbik_clip_shapes_layers_kernel(ShapeView v, int64_t total, const ClipLayer *layers, int K,
 		uint32_t flags, float *weights_out) {
 	const int64_t b0 = (int64_t)blockIdx.x * kShapeThreads;
 	const int t = threadIdx.x;
 	if (b0 + t >= total) return;
 	const BatchLane ln = batch_lane(v.P, b0, t);
-	weights_out[b0 + t] = shape_layers(v, layers + ln.s * K, K, flags, ln.item);
+	weights_out[b0 + t] = shape_layers<CUBIC>(v, layers + ln.s * K, K, flags, ln.item);
 }
 } // namespace
 
 namespace mbik {
 
-hipError_t launch_clip_shapes(hipStream_t st, const ShapeView &v, int64_t total_weights, const double *time, const int32_t *clip_index,
+hipError_t launch_clip_shapes(hipStream_t st, const ShapeView &v, bool cubic, int64_t total_weights, const double *time, const int32_t *clip_index,
 		int clip, float *weights_out) {
 	const unsigned blocks = (unsigned)((total_weights + kShapeThreads - 1) / kShapeThreads);
-	hipLaunchKernelGGL(mbik_clip_shapes_kernel, dim3(blocks), dim3(kShapeThreads), 0, st, v, total_weights, time, clip_index, clip,
+	hipLaunchKernelGGL(cubic ? mbik_clip_shapes_kernel<true> : mbik_clip_shapes_kernel<false>, dim3(blocks), dim3(kShapeThreads), 0, st, v, total_weights, time, clip_index, clip,
 			weights_out);
 	return hipGetLastError();
 }
 
-hipError_t launch_clip_shapes_layers(hipStream_t st, const ShapeView &v, int64_t total_weights, const ClipLayer *layers, int layer_count,
+hipError_t launch_clip_shapes_layers(hipStream_t st, const ShapeView &v, bool cubic, int64_t total_weights, const ClipLayer *layers, int layer_count,
 		uint32_t flags, float *weights_out) {
 	const unsigned blocks = (unsigned)((total_weights + kShapeThreads - 1) / kShapeThreads);
-	hipLaunchKernelGGL(mbik_clip_shapes_layers_kernel, dim3(blocks), dim3(kShapeThreads), 0, st, v, total_weights, layers, layer_count, flags,
+	hipLaunchKernelGGL(cubic ? mbik_clip_shapes_layers_kernel<true> : mbik_clip_shapes_layers_kernel<false>, dim3(blocks), dim3(kShapeThreads), 0, st, v, total_weights, layers, layer_count, flags,
 			weights_out);
 	return hipGetLastError();
 }

@@ -21,14 +21,17 @@
 #include "lds_copy.h"
 #include "root_motion.h"
 
+#include <type_traits>
+
 namespace {
 using namespace mbik;
 
 constexpr int kRootThreads = 64;
 
 // LV: the set's libm_variant, a compile-time constant of sin_f.  PLAIN: one (time, clip, 1.0f)
-// record a skeleton from time / clip_index / clip, flags 0; else [count][K] records.
-template <int LV, bool PLAIN>
+// record a skeleton from time / clip_index / clip, flags 0; else [count][K] records.  CUBIC: the
+// set has a cubic pose track (clip.h); a set without runs the <.., false> kernels.
+template <int LV, bool PLAIN, bool CUBIC>
 __global__ __launch_bounds__(kRootThreads) void mbik_root_motion_kernel(ClipView v, int count, int K, int root, const ClipLayer *layers,
 		const double *time_prev, const double *time, const int32_t *clip_index, int clip, uint32_t flags, float *motion_out, float *pose) {
 	__shared__ __attribute__((aligned(16))) float Ml[kRootThreads * 10];
@@ -41,10 +44,10 @@ __global__ __launch_bounds__(kRootThreads) void mbik_root_motion_kernel(ClipView
 		float *pose_s = pose ? pose + s * v.B * 10 : nullptr;
 		if constexpr (PLAIN) {
 			const RootPlain src{ClipLayer{time[s], clip_index ? clip_index[s] : clip, 1.0f}, time_prev[s]};
-			root_motion_skeleton(v, src, 1, 0u, root, LV, Ml + t * 10, pose_s);
+			root_motion_skeleton<CUBIC>(v, src, 1, 0u, root, LV, Ml + t * 10, pose_s);
 		} else {
 			const RootLayers src{layers + s * K, time_prev + s * K};
-			root_motion_skeleton(v, src, K, flags, root, LV, Ml + t * 10, pose_s);
+			root_motion_skeleton<CUBIC>(v, src, K, flags, root, LV, Ml + t * 10, pose_s);
 		}
 	}
 	__syncthreads();
@@ -74,7 +77,7 @@ __device__ __forceinline__ RootStep get_step(const float *p) {
 	return RootStep{q4(p[0], p[1], p[2], p[3]), v3(p[4], p[5], p[6]), v3(p[7], p[8], p[9])};
 }
 
-template <int LV>
+template <int LV, bool CUBIC>
 __global__ __launch_bounds__(kRootThreads) void mbik_root_motion_lanes_kernel(ClipView v, int count, int K, int root, const ClipLayer *layers,
 		const double *time_prev, uint32_t flags, float *motion_out, float *pose) {
 	__shared__ __attribute__((aligned(16))) float Ml[kRootThreads * 10];
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(kRootThreads) void mbik_root_motion_lanes_kernel(Cl
 		float *mine = Sl + t * kStepFloats;
 		int meta = 0;
 		if (valid && on) {
-			const RootLayerSteps ls = root_layer_steps(v, info, h, t0, rec.time, rec.weight, normalize, tot_pos, tot_rot, tot_scl, LV);
+			const RootLayerSteps ls = root_layer_steps<CUBIC>(v, info, h, t0, rec.time, rec.weight, normalize, tot_pos, tot_rot, tot_scl, LV);
 			meta = ls.segments | (ls.do_pos ? 4 : 0) | (ls.do_rot ? 8 : 0) | (ls.do_scl ? 16 : 0);
 			if (ls.segments > 0) put_step(mine + 1, ls.first);
 			if (ls.segments > 1) put_step(mine + 11, ls.second);
@@ -176,19 +179,24 @@ __global__ __launch_bounds__(kApplyThreads) void mbik_root_apply_kernel(int coun
 
 namespace mbik {
 
-hipError_t launch_root_motion(hipStream_t st, const ClipView &v, int libm, int count, int layer_count, int root, const ClipLayer *layers,
+hipError_t launch_root_motion(hipStream_t st, const ClipView &v, int libm, bool cubic, int count, int layer_count, int root, const ClipLayer *layers,
 		const double *time_prev, const double *time, const int32_t *clip_index, int clip, uint32_t flags, float *motion_out, float *pose) {
 	const bool sse2 = libm == LIBM_SSE2;
 	if (MBIK_ROOT_LANE_PER_LAYER && layers && layer_count > 1) {
 		const int per_block = kRootThreads / layer_count;
 		const unsigned blocks = (unsigned)(((int64_t)count + per_block - 1) / per_block);
-		const auto kernel = sse2 ? mbik_root_motion_lanes_kernel<LIBM_SSE2> : mbik_root_motion_lanes_kernel<LIBM_FMA>;
+		const auto kernel = cubic ? (sse2 ? mbik_root_motion_lanes_kernel<LIBM_SSE2, true> : mbik_root_motion_lanes_kernel<LIBM_FMA, true>)
+								  : (sse2 ? mbik_root_motion_lanes_kernel<LIBM_SSE2, false> : mbik_root_motion_lanes_kernel<LIBM_FMA, false>);
 		hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kRootThreads), 0, st, v, count, layer_count, root, layers, time_prev, flags, motion_out, pose);
 		return hipGetLastError();
 	}
 	const unsigned blocks = (unsigned)(((int64_t)count + kRootThreads - 1) / kRootThreads);
-	const auto kernel = layers ? (sse2 ? mbik_root_motion_kernel<LIBM_SSE2, false> : mbik_root_motion_kernel<LIBM_FMA, false>)
-								: (sse2 ? mbik_root_motion_kernel<LIBM_SSE2, true> : mbik_root_motion_kernel<LIBM_FMA, true>);
+	const auto plain = [&](auto c) {
+		constexpr bool CUBIC = decltype(c)::value;
+		return layers ? (sse2 ? mbik_root_motion_kernel<LIBM_SSE2, false, CUBIC> : mbik_root_motion_kernel<LIBM_FMA, false, CUBIC>)
+					  : (sse2 ? mbik_root_motion_kernel<LIBM_SSE2, true, CUBIC> : mbik_root_motion_kernel<LIBM_FMA, true, CUBIC>);
+	};
+	const auto kernel = cubic ? plain(std::true_type{}) : plain(std::false_type{});
 	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kRootThreads), 0, st, v, count, layer_count, root, layers, time_prev, time, clip_index, clip,
 			flags, motion_out, pose);
 	return hipGetLastError();

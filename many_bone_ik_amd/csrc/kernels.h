@@ -215,21 +215,22 @@ hipError_t launch_cull_lod(hipStream_t st, int count, const float *boxes, const 
 hipError_t launch_blend(hipStream_t st, int64_t total_bones, int B, int libm, float influence, const float *influence_per_skeleton,
 		const float *pose_in, const float *pose_mod, float *pose_out);
 // k_clip.hip: mbik_clip_sample (clip.h).  One thread per bone of the total_bones = count * v.B, 256 bones a block, 10 KiB of
-// static LDS; v's tables are device memory; clip_index (device, [count]) overrides clip when given.
+// static LDS; v's tables are device memory; clip_index (device, [count]) overrides clip when given.  cubic (here and in
+// the launches below): v holds a track with kClipCubic, which selects the kernels' CUBIC instantiation.
 struct ClipView;
-hipError_t launch_clip(hipStream_t st, const ClipView &v, int libm, int64_t total_bones, const double *time, const int32_t *clip_index,
+hipError_t launch_clip(hipStream_t st, const ClipView &v, int libm, bool cubic, int64_t total_bones, const double *time, const int32_t *clip_index,
 		int clip, float *pose_out);
 // k_clip.hip: mbik_clip_sample_layers (clip_layers.h).  The same shape; layers is device memory, [count][layer_count]
 // records of 16 bytes, 8-byte aligned; layer_count in [1, 8]; the kernel tests every record's clip index itself.
 struct ClipLayer;
-hipError_t launch_clip_layers(hipStream_t st, const ClipView &v, int libm, int64_t total_bones, const ClipLayer *layers, int layer_count,
+hipError_t launch_clip_layers(hipStream_t st, const ClipView &v, int libm, bool cubic, int64_t total_bones, const ClipLayer *layers, int layer_count,
 		uint32_t flags, float *pose_out);
 // k_clip_shapes.hip: mbik_clip_sample_shapes and mbik_clip_sample_shapes_layers (clip_shapes.h).  One thread per weight of the
 // total_weights = count * v.P, 256 weights a block, no LDS; the arguments otherwise as the two launches above.
 struct ShapeView;
-hipError_t launch_clip_shapes(hipStream_t st, const ShapeView &v, int64_t total_weights, const double *time, const int32_t *clip_index,
+hipError_t launch_clip_shapes(hipStream_t st, const ShapeView &v, bool cubic, int64_t total_weights, const double *time, const int32_t *clip_index,
 		int clip, float *weights_out);
-hipError_t launch_clip_shapes_layers(hipStream_t st, const ShapeView &v, int64_t total_weights, const ClipLayer *layers, int layer_count,
+hipError_t launch_clip_shapes_layers(hipStream_t st, const ShapeView &v, bool cubic, int64_t total_weights, const ClipLayer *layers, int layer_count,
 		uint32_t flags, float *weights_out);
 // k_root_motion.hip: mbik_clip_root_motion[_layers] and mbik_root_motion_apply (root_motion.h).  The plain form and a call
 // with one layer: one thread per skeleton, 64 skeletons a block, 2.5 KiB of static LDS; 2 to 8 layers: a lane per (skeleton,
@@ -237,7 +238,7 @@ hipError_t launch_clip_shapes_layers(hipStream_t st, const ShapeView &v, int64_t
 // [count][layer_count]; layers null: the plain form, time / time_prev [count] and clip_index or clip.  pose ([count][v.B][10])
 // may be null.  The kernels test every clip index themselves.  The apply kernel works on skeleton_global [count][12] in
 // place, no LDS.
-hipError_t launch_root_motion(hipStream_t st, const ClipView &v, int libm, int count, int layer_count, int root, const ClipLayer *layers,
+hipError_t launch_root_motion(hipStream_t st, const ClipView &v, int libm, bool cubic, int count, int layer_count, int root, const ClipLayer *layers,
 		const double *time_prev, const double *time, const int32_t *clip_index, int clip, uint32_t flags, float *motion_out, float *pose);
 hipError_t launch_root_apply(hipStream_t st, int count, const float *motion, uint32_t flags, float *skeleton_global);
 // k_playback.hip: mbik_playback_advance (playback.h).  One thread per skeleton, 64 skeletons a block; one layer: no LDS; 2 to 8

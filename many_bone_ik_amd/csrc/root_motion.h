@@ -33,7 +33,8 @@ struct RootPlain {
 
 // The root's channels at both ends of one segment (u0, u1) of already mapped times, or NaN for a
 // layer whose times are not finite.  Both ends search in step -- six independent loads a step --
-// and their twenty-four key loads are issued before either end is evaluated.
+// and their twenty-four key loads (forty-eight with CUBIC) are issued before either end is evaluated.
+template <bool CUBIC = false>
 GDI void root_segment(const ClipView &v, const ClipInfo &info, const ClipLayerHeaders &h, bool finite, double u0, double u1, int lv,
 		ClipSampled &x0, ClipSampled &x1) {
 	if (!finite) { // no key is read
@@ -51,9 +52,15 @@ GDI void root_segment(const ClipView &v, const ClipInfo &info, const ClipLayerHe
 		clip_search_step(p0, r0, s0, step, u0);
 		clip_search_step(p1, r1, s1, step, u1);
 	}
-	const ClipLoaded k0 = clip_load(p0, r0, s0), k1 = clip_load(p1, r1, s1);
-	clip_eval(k0, r0.n, u0, info.length, lv, x0);
-	clip_eval(k1, r1.n, u1, info.length, lv, x1);
+	if constexpr (CUBIC) {
+		const ClipLoadedCubic k0 = clip_load_cubic(p0, r0, s0), k1 = clip_load_cubic(p1, r1, s1);
+		clip_eval_cubic(k0, r0.n, u0, info.length, lv, x0);
+		clip_eval_cubic(k1, r1.n, u1, info.length, lv, x1);
+	} else {
+		const ClipLoaded k0 = clip_load(p0, r0, s0), k1 = clip_load(p1, r1, s1);
+		clip_eval(k0, r0.n, u0, info.length, lv, x0);
+		clip_eval(k1, r1.n, u1, info.length, lv, x1);
+	}
 }
 
 // What one layer adds over one segment: the position and scale differences times their blend
@@ -80,6 +87,7 @@ struct RootLayerSteps {
 	bool do_pos, do_rot, do_scl;
 	RootStep first, second;
 };
+template <bool CUBIC = false>
 GDI RootLayerSteps root_layer_steps(const ClipView &v, const ClipInfo &info, ClipLayerHeaders h, double t0, double t1, float weight,
 		bool normalize, float tot_pos, float tot_rot, float tot_scl, int lv) {
 	RootLayerSteps out;
@@ -100,11 +108,11 @@ GDI RootLayerSteps root_layer_steps(const ClipView &v, const ClipInfo &info, Cli
 	if (finite) p0 = clip_time(t0, info.length, info.loop_mode), p1 = clip_time(t1, info.length, info.loop_mode);
 	const bool looped = finite && info.loop_mode == 1 && p0 > p1;
 	ClipSampled x0, x1;
-	root_segment(v, info, h, finite, p0, looped ? info.length : p1, lv, x0, x1);
+	root_segment<CUBIC>(v, info, h, finite, p0, looped ? info.length : p1, lv, x0, x1);
 	out.first = root_step(x0, x1, out.do_pos, out.do_rot, out.do_scl, bp, br, bs, lv);
 	out.segments = 1;
 	if (looped) {
-		root_segment(v, info, h, true, 0.0, p1, lv, x0, x1);
+		root_segment<CUBIC>(v, info, h, true, 0.0, p1, lv, x0, x1);
 		out.second = root_step(x0, x1, out.do_pos, out.do_rot, out.do_scl, bp, br, bs, lv);
 		out.segments = 2;
 	}
@@ -150,7 +158,7 @@ GDI bool root_motion_valid(const Src &src, int K, int clip_count) {
 // time, clip info and headers before layer l's keys are searched.
 // (k_root_motion.hip also has a form that gives each layer a lane of its own: the same
 // root_layer_steps, root_add and root_store, the totals and the sums in the same order.)
-template <class Src>
+template <bool CUBIC = false, class Src>
 GDI void root_motion_record(const ClipView &v, const Src &src, int K, uint32_t flags, int root, int lv, float *out10) {
 	const bool normalize = (flags & kClipLayersNormalize) != 0;
 	float tot_pos = 0.0f, tot_rot = 0.0f, tot_scl = 0.0f;
@@ -184,7 +192,7 @@ GDI void root_motion_record(const ClipView &v, const Src &src, int K, uint32_t f
 			next_info = v.clips[next.clip == kClipLayerOff ? 0 : next.clip];
 		}
 		if (rec.clip == kClipLayerOff) continue;
-		const RootLayerSteps ls = root_layer_steps(v, info, h, t0, rec.time, rec.weight, normalize, tot_pos, tot_rot, tot_scl, lv);
+		const RootLayerSteps ls = root_layer_steps<CUBIC>(v, info, h, t0, rec.time, rec.weight, normalize, tot_pos, tot_rot, tot_scl, lv);
 		if (ls.segments > 0) root_add(a, ls.first, ls.do_pos, ls.do_rot, ls.do_scl);
 		if (ls.segments > 1) root_add(a, ls.second, ls.do_pos, ls.do_rot, ls.do_scl);
 	}
@@ -193,7 +201,7 @@ GDI void root_motion_record(const ClipView &v, const Src &src, int K, uint32_t f
 
 // One skeleton, steps 1 to 7: its record, ten NaNs for an invalid one, and the rest pose's root
 // record into pose_s ([B][10], or null) for a valid one.
-template <class Src>
+template <bool CUBIC = false, class Src>
 GDI void root_motion_skeleton(const ClipView &v, const Src &src, int K, uint32_t flags, int root, int lv, float *out10, float *pose_s) {
 	if (!root_motion_valid(src, K, v.clip_count)) {
 		for (int f = 0; f < 10; f++) out10[f] = clip_nan();
@@ -203,7 +211,7 @@ GDI void root_motion_skeleton(const ClipView &v, const Src &src, int K, uint32_t
 		const float *rest = v.rest + (int64_t)root * 10;
 		for (int f = 0; f < 10; f++) pose_s[(int64_t)root * 10 + f] = rest[f];
 	}
-	root_motion_record(v, src, K, flags, root, lv, out10);
+	root_motion_record<CUBIC>(v, src, K, flags, root, lv, out10);
 }
 
 // One skeleton's world transform G [12] (basis rows, then origin) times the motion record's
